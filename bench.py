@@ -13,11 +13,21 @@ Inside a rank the share is dealt, longest first, to E engines (own stream + host
 an engine decodes its share as ONE queue with lane refill (s3a_uttdec_decode_queue_dev: a lane takes the next utterance
 when its own has ended); a share of no more utterances than lanes (--refill 0: any share) runs as groups of similar
 length in lock step.  Features are resident in HBM before the timed region; history tables and hypotheses come back inside it.
-Arithmetic is the bit-exact mode (float32 subtract, float64 accumulate, int32 log-add).  After the timed region rank 0
-formats the LAST step's gathered hypotheses and compares every -hyp / -hypseg line with the unmodified reference
-decoder's (CPU, same files); a difference is an error, not a number.
+Arithmetic is the bit-exact mode (float32 subtract, float64 accumulate, int32 log-add).  With --full, after the timed
+region rank 0 formats the LAST step's gathered hypotheses and compares every -hyp / -hypseg line with the unmodified
+reference decoder's (CPU, same files); a difference is an error, not a number.
+
+A plain run (no --full) sets up, warms up, times the steps, writes the last step's outputs if --dump-outputs DIR is
+given, and prints the headline line: no reference decodes, no CPU baseline, no extra legs or per-kernel figures.  Its
+decode_calls_timed counts the decode calls the timed steps made (with lane refill: one per engine and step).
+--full adds all of those (the keys below); --plain, --only-scoring, --check-all and --cpu-physical imply it.
+--dump-outputs DIR writes what the last timed step returned to its caller -- every utterance's hypothesis header and
+words, in utterance order -- as DIR/<name>.npy (float64; the values are int32): utt_index, utt_n_words, utt_n_frames,
+utt_score, utt_total_scale, utt_n_entry, utt_status, utt_exit_id [utterances], words [sum of n_words, 6: wid sf ef
+ascr lscr scale].  The task is seeded: the same arguments give the same inputs in every run.
 
     python bench.py --gpus 1 --steps 2 --warmup 1
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -25,7 +35,7 @@ The decoder is rebuilt from a bundle (cmusphinx_amd/bundle.py) through the C ABI
 (oracle/_ref/ref_s3amd_tst_decode = integration/sphinx3 + the unmodified reference's kb_init) runs once, UNTIMED, to load
 the models / dictionary / LM, build the lextrees and write that bundle.
 
-Prints ONE JSON line (rank 0).  Extra keys beyond the driver contract:
+Prints ONE JSON line (rank 0).  Extra keys beyond the driver contract (--full):
   roofline      the dominant kernel of a frame IN THE BENCH (HIP events around every launch of every 8th frame of every engine
                 while all engines run; the look-ahead scoring launch counted per frame it serves): achieved = algorithmic
                 bytes (or flops) per launch / average launch time; `alone` = the same with one engine on the chip; traffic =
@@ -64,6 +74,9 @@ FP64_VEC_PEAK_TFLOPS = 78.6     # MI355X FP64 vector peak (FMA counted as 2 flop
 REFDEC = os.path.join(ROOT, "oracle", "_ref", "sphinx3_decode")
 SHIM = os.path.join(ROOT, "oracle", "_ref", "ref_s3amd_tst_decode")
 PMC_FILE = os.path.join(ROOT, "profiles", "pmc_traffic.json")     # tools/gpu_round6.sh: HBM bytes per lane-frame of ku_frames (PMC passes)
+METRIC = "decoded_frames_per_sec (full mode-4 decode, hub4-shaped CD-GMM 6144x8x39 + 20k-word lextrees + trigram; xRT = value/100/n_gpus)"
+DTYPE_EXACT = "f32-sub/f64-acc/int32-logadd (bit-exact), int32 Viterbi + word level"
+DTYPE_FAST = "f32 scoring (+-2 logs3), int32 search"
 
 
 def csrc_hash():
@@ -435,6 +448,54 @@ def ps_fwdtree_leg(t, lanes, n_cpu=128, n_proc=16):
     return out
 
 
+def make_task_and_bundle(d, n_utt, n_frames, bpath, overlap):
+    """The synthetic task under d and the decoder bundle the drop-in exports from it (kb_init reads the model, dictionary
+    and LM only).  overlap: the export starts as soon as make_task has written those files -- it writes the utterances'
+    features last, the first of them once the LM file is closed -- and runs while the features are generated.  (A rank of a
+    multi-rank run reads the control file before kb_init: there the export waits for the whole task.)"""
+    import shutil
+    import threading
+    from cmusphinx_amd import synth_task
+    cmd = [SHIM] + synth_task.decoder_args(d)
+    env = dict(os.environ, S3A_UTT="1", S3A_EXPORT=bpath)
+    make = lambda: synth_task.make_task(d, n_utt=n_utt, n_frames=n_frames, sorted_names=True, **synth_task.HUB4_TASK)
+    if not overlap:
+        make()
+        r = subprocess.run(cmd, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        assert r.returncode == 0 and os.path.exists(bpath), "bundle export failed"
+        return
+    shutil.rmtree(os.path.join(d, "feat"), ignore_errors=True)
+    first = os.path.join(d, "feat", "utt0000.mfc")
+    err = []
+
+    def gen():
+        try:
+            make()
+        except BaseException as e:          # (re-raised on the calling thread)
+            err.append(e)
+    th = threading.Thread(target=gen)
+    th.start()
+    while th.is_alive() and not os.path.exists(first):
+        time.sleep(0.01)
+    p = subprocess.Popen(cmd, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL) if not err else None
+    th.join()
+    rc = p.wait() if p is not None else None
+    if err:
+        raise err[0]
+    assert rc == 0 and os.path.exists(bpath), "bundle export failed"
+
+
+def dump_outputs(out_dir, recs):
+    """--dump-outputs: the hypotheses the timed path returned (rank 0's gathered records, utterance order) as float64 .npy"""
+    os.makedirs(out_dir, exist_ok=True)
+    keys = ("utt_index", "n_words", "n_frames", "score", "total_scale", "n_entry", "status", "exit_id")
+    for k in keys:
+        name = k if k.startswith("utt_") else f"utt_{k}"
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.array([getattr(h, k) for h, _ in recs], np.float64))
+    words = [np.asarray(w, np.int32).reshape(-1, 6) for _, w in recs]
+    np.save(os.path.join(out_dir, "words.npy"), (np.concatenate(words) if words else np.zeros((0, 6), np.int32)).astype(np.float64))
+
+
 def exchange_run_id(dist, rank, tdev):
     """the run id of the C exchange's rendezvous (s3a_gather_init_run): the launcher's S3A_RUN_ID (launch_ranks draws one per launch);
     under a foreign launcher (torch.distributed.run: only MASTER_PORT, the same from run to run) rank 0 draws a number and
@@ -520,7 +581,14 @@ def main():
     ap.add_argument("--fast", action="store_true", help="S3A_GMM_FAST (f32, +-2 logs3 units) instead of bit-exact")
     ap.add_argument("--variant", action="append", default=[], metavar="FIELD=INT",
             help="a field of s3a_variants_t (s3a_set_variants), e.g. hist_sort_launch=1: A/B runs of kernel variants")
+    ap.add_argument("--full", action="store_true",
+            help="everything beyond the headline: the reference decodes and the comparison with them, the CPU baseline, the per-kernel "
+                 "and roofline figures, the projection, the single utterance, the extra legs, weak scaling (several GPUs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+            help="write the last timed step's hypotheses (headers and words, float64) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.plain or args.only_scoring or args.check_all or args.cpu_physical:
+        args.full = True
     if args.plain:
         args.no_cpu = args.no_scoring = args.no_ps = args.no_wide_beam = True
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -570,10 +638,7 @@ def main():
         os.makedirs(d, exist_ok=True)
         if os.path.exists(os.path.join(d, "rccl-id")):
             os.remove(os.path.join(d, "rccl-id"))
-        synth_task.make_task(d, n_utt=U, n_frames=T, sorted_names=True, **synth_task.HUB4_TASK)
-        r = subprocess.run([SHIM] + synth_task.decoder_args(d), env=dict(os.environ, S3A_UTT="1", S3A_EXPORT=bpath),
-                           stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        assert r.returncode == 0 and os.path.exists(bpath), "bundle export failed"
+        make_task_and_bundle(d, U, T, bpath, overlap=world == 1)
     if dist is not None:
         dist.barrier()
     targs = synth_task.decoder_args(d)
@@ -646,6 +711,7 @@ def main():
         return list(range(U)), rank * U              # weak: a whole batch per rank (record ids offset by the rank)
 
     host_t = {}
+    calls = {"decode": 0}                  # decode calls (a group or a queue part of an engine) made by run_step
 
     def run_step(step, recs=None, sched=None):
         ids, base = my_share(step)
@@ -653,8 +719,9 @@ def main():
 
         def one(e):         # engine e decodes its groups one after the other (the C calls release the GIL)
             lib.check(L.s3a_set_device(local_rank))     # (HIP's current device is per host thread)
-            ms, out, t_dec, t_hyp = 0.0, [], 0.0, 0.0
+            ms, out, t_dec, t_hyp, n = 0.0, [], 0.0, 0.0, 0
             for g in per[e]:
+                n += 1
                 t0 = time.perf_counter()
                 refill = args.refill and len(g) > NLE
                 if refill:
@@ -667,18 +734,19 @@ def main():
                     out += [get(z, utts[k], base + k) for z, k in enumerate(g)]
                 t_dec += t1 - t0
                 t_hyp += time.perf_counter() - t1
-            return ms, out, t_dec, t_hyp
+            return ms, out, t_dec, t_hyp, n
         done = list(pool.map(one, range(NE))) if NE > 1 else [one(0)]     # (one engine: on the calling thread)
         if recs is not None:
             for d_ in done:
                 recs.extend(d_[1])
         host_t["decode_call_s"] = max(d_[2] for d_ in done)
         host_t["hyp_s"] = max(d_[3] for d_ in done)
+        calls["decode"] += sum(d_[4] for d_ in done)
         return max(d_[0] for d_ in done)
 
     # ---------------- the reference (rank 0, untimed): CPU baseline + what the device's output is compared with ----------------
     cpu, ref = None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         n_procs = max(1, args.cpu_procs)
         if args.no_cpu:
             one = cpu_batch(targs, ctl, d, min(2, U), 1, "gate_")
@@ -721,6 +789,7 @@ def main():
         run_step(i)
     sync_all()
     dev_ms, allrec = 0.0, None
+    calls["decode"] = 0
     t0 = time.perf_counter()
     for i in range(args.steps):
         recs = []
@@ -733,11 +802,31 @@ def main():
             allrec = sorted(recs, key=lambda t: t[0].utt_index)
     sync_all()
     dt = time.perf_counter() - t0
+    decode_calls_timed = calls["decode"]
     if dist is not None:
         import torch
         tmax = torch.tensor([dt], dtype=torch.float64, device=tdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+
+    if rank == 0:
+        assert len(allrec) == n_total and all(h.status == 0 for h, _ in allrec)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, allrec)
+    if not args.full:
+        if rank == 0:
+            frames_step = sum(h.n_frames for h, _ in allrec)
+            value = frames_step * args.steps / dt
+            print(json.dumps({
+                "metric": METRIC, "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": args.scaling,
+                "dtype": DTYPE_FAST if args.fast else DTYPE_EXACT,
+                "config": {"utterances_per_step": n_total, "frames_per_step": frames_step, "lanes_per_gpu": NL, "engines_per_gpu": NE},
+                "xRT_per_gpu": round(value / world / 100.0, 1), "device_ms_per_step": round(dev_ms / args.steps, 3),
+                "decode_calls_timed": decode_calls_timed, "load_s": round(t_load, 2), "setup_s": round(t_setup, 1), "full": False}))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     weak = None
     if world > 1 and args.scaling == "strong":
@@ -757,7 +846,6 @@ def main():
         args.scaling = "strong"
 
     if rank == 0:
-        assert len(allrec) == n_total and all(h.status == 0 for h, _ in allrec)
         frames_step = sum(h.n_frames for h, _ in allrec)
         value = frames_step * args.steps / dt
         # ---- the gate: the LAST timed step's hypotheses, every line against the unmodified reference decoder's ----
@@ -966,10 +1054,10 @@ def main():
             del one
 
         res = {
-            "metric": "decoded_frames_per_sec (full mode-4 decode, hub4-shaped CD-GMM 6144x8x39 + 20k-word lextrees + trigram; xRT = value/100/n_gpus)",
+            "metric": METRIC,
             "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "f32-sub/f64-acc/int32-logadd (bit-exact), int32 Viterbi + word level" if not args.fast else "f32 scoring (+-2 logs3), int32 search",
+            "dtype": DTYPE_EXACT if not args.fast else DTYPE_FAST,
             "data": f"synthetic (seeded hub4-shaped model, dictionary, ARPA trigram; {U} DISTINCT ~10 s utterances sampled from the model "
                     "along LM sentences; real hub4 parameters are not in the reference checkout); features resident in HBM before the "
                     "timed region (the CPU baseline reads its feature files)",

@@ -48,7 +48,11 @@ def _phone_names(n_ciphone, sorted_names=False):
 def make_task(dirpath, n_sen, n_ciphone, n_comp, n_words, seed, n_utt=4, n_frames=1000,
               sep=1.0, noise=1.0, ctx_keep=0.5, n_emit=3, sorted_names=False):
     """Write the task under dirpath; returns a dict describing it (paths, args, truth).  n_emit = emitting states per
-    HMM: 3 (hub4 / WSJ / RM1 / tidigits) or 5 (Bakis topology with skip transitions: hmm_vit_eval_5st_lr)."""
+    HMM: 3 (hub4 / WSJ / RM1 / tidigits) or 5 (Bakis topology with skip transitions: hmm_vit_eval_5st_lr).
+
+    Write order: dict, fillerdict, mdef, the model parameters and lm.arpa are closed before feat/utt0000.mfc is opened, and
+    the control file comes last.  bench.py (make_task_and_bundle) starts the decoder export, which reads the model,
+    dictionary and LM only, as soon as the first feature file appears: keep that order."""
     N_EMIT = n_emit
     rng = np.random.Generator(np.random.PCG64(seed))
     os.makedirs(os.path.join(dirpath, "feat"), exist_ok=True)

@@ -1,12 +1,14 @@
 """The pocketsphinx first-pass cases shared by tests/test_oracle_psfwd.py (restatement vs unmodified pocketsphinx, CPU)
 and tests/test_gpu_psfwd.py (device vs unmodified pocketsphinx, MI355X).  Every case is a command line of
 oracle/ref_ps_fwd.c's drivers over data held under tests/golden/ (model files, dictionaries, LMs, cepstra and audio the
-reference's own tests hold) or tests/_local_data/ps (tools/fetch_local_data.sh: the larger ones, git-ignored)."""
+reference's own tests hold; the larger ones are committed compressed under tests/golden/ps and written out into
+tests/_local_data/ps by tests/local_data.py)."""
 import os
 import subprocess
 
 import pytest
 
+import local_data
 import psfwd_dump
 from conftest import GOLDEN, ROOT
 
@@ -48,14 +50,14 @@ def sc_args(tmp_path):
 
 
 def turtle_args(tmp_path, utts=("goforward",)):
-    need(os.path.join(LOCAL, "hub4wsj_sc_8k", "mdef"))
+    local_data.path("ps")
     ctl = ctl_file(tmp_path, "raw.ctl", utts)
     return ["-hmm", f"{LOCAL}/hub4wsj_sc_8k", "-lm", f"{TUR}/turtle.DMP", "-dict", f"{TUR}/turtle.dic", "-ctl", ctl,
             "-cepdir", f"{LOCAL}/raw", "-cepext", ".raw", "-adcin", "yes"]
 
 
 def zh_args(tmp_path, utts=("goforward", "numbers", "something")):
-    need(os.path.join(LOCAL, "zh_CN", "gigatdt.5000.DMP"))
+    local_data.path("ps")
     ctl = ctl_file(tmp_path, "raw.ctl", utts)
     return ["-hmm", f"{LOCAL}/tdt_sc_8k", "-lm", f"{LOCAL}/zh_CN/gigatdt.5000.DMP", "-dict", f"{LOCAL}/zh_CN/mandarin_notone.dic",
             "-ctl", ctl, "-cepdir", f"{LOCAL}/raw", "-cepext", ".raw", "-adcin", "yes"]

@@ -3,7 +3,8 @@ ps_decode_raw (plumbing, no GPU)".  The UNMODIFIED pocketsphinx (oracle/_ref/lib
 ps_init / ps_decode_raw / ps_get_hyp (oracle/ref_ps_raw.c) -- on the reference's own audio with the US-English PTM
 model of the checkout (pocketsphinx-extra/model/hmm/en_US/hub4_wsj_ptm256_3s_8k.cd_ptm_5000) and
 goforward.fsg: the hypothesis pocketsphinx/test/unit/test_fsg.c:21-70 expects, and the path score the survey's probe
-recorded.  Runs where /root/reference exists (model and audio are not redistributed); nothing of ours is in the path:
+recorded.  The models and goforward.fsg are committed compressed (tests/golden/ps_ptm, tests/golden/ps: tests/local_data.py),
+the dictionary and the audio are tests/golden/ps_turtle; needs the reference build (oracle/_ref); nothing of ours is in the path:
 it pins what the ps_decoder_t utterance API returns for the secondary boundary (ps_mgaufuncs_t, tests/test_gpu_psms.py).
 """
 import os
@@ -11,20 +12,22 @@ import subprocess
 
 import pytest
 
-from conftest import ROOT
+import local_data
+from conftest import GOLDEN, ROOT
 
-REF = "/root/reference"
 EXE = os.path.join(ROOT, "oracle", "_ref", "ref_ps_raw")
-PTM = f"{REF}/pocketsphinx-extra/model/hmm/en_US/hub4_wsj_ptm256_3s_8k.cd_ptm_5000"
-SC = f"{REF}/pocketsphinx/model/hmm/en_US/hub4wsj_sc_8k"
+TUR = os.path.join(GOLDEN, "ps_turtle")
+PTM = ("ps_ptm", "hub4_wsj_ptm256_3s_8k.cd_ptm_5000")
+SC = ("ps", "hub4wsj_sc_8k")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference checkout (model + audio are not redistributed)")
-@pytest.mark.parametrize("hmm,score", [(PTM, -3003), (SC, None)])
+@pytest.mark.skipif(not os.path.isdir(os.path.join(ROOT, "oracle", "_ref")), reason="needs the reference build (oracle/_ref)")
+@pytest.mark.parametrize("hmm,score", [(PTM, -3003), (SC, None)], ids=["ptm", "sc"])
 def test_ps_decode_raw_goforward(hmm, score):
     assert os.path.exists(EXE), "make -C oracle ref"
-    p = subprocess.run([EXE, hmm, f"{REF}/pocketsphinx/test/data/goforward.fsg", f"{REF}/pocketsphinx/model/lm/en/turtle.dic",
-                        f"{REF}/pocketsphinx/test/data/goforward.raw"], capture_output=True, text=True, timeout=300)
+    fsg = os.path.join(local_data.path("ps_ptm"), "goforward.fsg")
+    p = subprocess.run([EXE, os.path.join(local_data.path(hmm[0]), hmm[1]), fsg, f"{TUR}/turtle.dic", f"{TUR}/goforward.raw"],
+                       capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-400:]
     assert "HYP: go forward ten meters (goforward " in p.stdout
     if score is not None:       # the PTM model: the path score of the survey's probe

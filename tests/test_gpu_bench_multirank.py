@@ -19,7 +19,7 @@ def run_bench(tmp_path, port, extra):
     env = dict(os.environ, S3A_BENCH_ONE_GPU="1", TMPDIR=str(tmp_path))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--lanes", "6", "--engines", "2", "--min-group", "2", "--frames", "150", "--utts", "10", "--no-scoring"] + extra
+           "--lanes", "6", "--engines", "2", "--min-group", "2", "--frames", "150", "--utts", "10", "--no-scoring", "--full"] + extra
     p = subprocess.run(cmd, capture_output=True, text=True, errors="ignore", timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -59,7 +59,7 @@ def test_bench_starts_its_ranks_itself(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--lanes", "6", "--engines", "2",
-           "--min-group", "2", "--frames", "150", "--utts", "10", "--no-scoring", "--no-cpu", "--no-ps", "--no-wide-beam"]
+           "--min-group", "2", "--frames", "150", "--utts", "10", "--no-scoring", "--no-cpu", "--no-ps", "--no-wide-beam", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, errors="ignore", timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -15,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import local_data
 from cmusphinx_amd import bundle, lib, s3io
 from conftest import GOLDEN, ROOT
 
@@ -35,6 +36,7 @@ def tidigits_args():
 
 
 def rm_args(n=20):
+    local_data.path("rm1")
     return ["-mdef", f"{RM}/mdef", "-fdict", f"{RM}/fillerdict", "-dict", f"{RM}/RM.dictionary", "-mean", f"{RM}/means",
             "-var", f"{RM}/variances", "-mixw", f"{RM}/mixture_weights", "-tmat", f"{RM}/transition_matrices",
             "-agc", "none", "-varnorm", "no", "-cmn", "current", "-epl", "4", "-fillprob", "0.02", "-maxwpf", "10",
@@ -56,8 +58,6 @@ def export(args, path):
 def bundles(tmp_path_factory):
     d = tmp_path_factory.mktemp("dagb")
     out = {"tidigits": export(tidigits_args(), str(d / "t.bundle"))}
-    if not os.path.isdir(RM):
-        pytest.fail(f"{RM} is missing on the GPU box (tools/fetch_local_data.sh)")
     out["rm1"] = export(rm_args(), str(d / "r.bundle"))
     return out
 

@@ -20,6 +20,7 @@ import sys
 
 import pytest
 
+import local_data
 from conftest import GOLDEN, ROOT
 
 pytestmark = pytest.mark.gpu
@@ -54,6 +55,7 @@ def common():
 
 @pytest.fixture(autouse=True)
 def _artefacts():
+    local_data.path("rm1")
     need(SHIM, REFDEC, TST, PSSHIM, RM)
 
 
@@ -186,15 +188,15 @@ def test_full_device_search_with_histogram_pruning(driver, tmp_path):
 
 # ---------------------------------------------------------------------------
 # RM1 (1935 senones, 6136-node lextrees with multi-parent first-level nodes, 997-word
-# trigram): data is NOT committed (8 MB of third-party model files); tools/
-# fetch_local_data.sh copies it from the reference checkout into tests/_local_data/,
-# which travels with the gpurun snapshot.  Here the expected output is produced LIVE by
-# the unmodified reference on the same box, so no golden file is needed.
+# trigram): the task's files are committed compressed under tests/golden/rm1/ and
+# written out by tests/local_data.py.  Here the expected output is produced LIVE by
+# the unmodified reference on the same machine, so no golden file is needed.
 # ---------------------------------------------------------------------------
 RM = os.path.join(ROOT, "tests", "_local_data", "rm1")
 
 
 def rm_args(extra=()):
+    local_data.path("rm1")
     return list(extra) + ["-mdef", f"{RM}/mdef", "-fdict", f"{RM}/fillerdict", "-dict", f"{RM}/RM.dictionary",
             "-mean", f"{RM}/means", "-var", f"{RM}/variances", "-mixw", f"{RM}/mixture_weights",
             "-tmat", f"{RM}/transition_matrices", "-agc", "none", "-varnorm", "no", "-cmn", "current",

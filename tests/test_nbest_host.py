@@ -83,8 +83,8 @@ RM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_local_data", "rm
 REFDEC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "sphinx3_decode")
 
 
-@pytest.mark.skipif(not (os.path.exists(REFDEC) and os.path.exists(os.path.join(RM, "rm.ctl"))),
-                    reason="needs the reference build (oracle/_ref) and the RM1 task (tools/fetch_local_data.sh): the build container")
+@pytest.mark.skipif(not os.path.exists(REFDEC),
+                    reason="needs the reference build (oracle/_ref)")
 @pytest.mark.parametrize("extra,meta", [(["-nbest", "40"], (40, 1e-140, 0.0)), (["-nbest", "25", "-bestpathlw", "11"], (25, 1e-140, 11.0))])
 def test_rm1_lists_live(extra, meta, tmp_path):
     """the same on RM1 (1 000 words, trigram, lists of 25 - 40 hypotheses, lattices of hundreds of links): the unmodified reference decodes

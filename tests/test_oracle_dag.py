@@ -13,6 +13,7 @@ import subprocess
 
 import pytest
 
+import local_data
 from conftest import GOLDEN, ROOT
 
 D = os.path.join(GOLDEN, "tidigits_decode")
@@ -38,6 +39,7 @@ def tidigits_args():
 
 
 def rm_args(n=20):
+    local_data.path("rm1")
     return ["-mdef", f"{RM}/mdef", "-fdict", f"{RM}/fillerdict", "-dict", f"{RM}/RM.dictionary", "-mean", f"{RM}/means",
             "-var", f"{RM}/variances", "-mixw", f"{RM}/mixture_weights", "-tmat", f"{RM}/transition_matrices",
             "-agc", "none", "-varnorm", "no", "-cmn", "current", "-epl", "4", "-fillprob", "0.02", "-maxwpf", "10",
@@ -68,7 +70,7 @@ def test_tidigits_second_pass_from_the_oracle_is_byte_identical(extra, tmp_path)
 
 @pytest.mark.parametrize("extra", [["-bestpath", "1"], ["-bestpath", "1", "-bestpathlw", "9.5"], ["-bestpath", "1", "-min_endfr", "0", "-maxwpf", "20"]])
 def test_rm1_second_pass_from_the_oracle_is_byte_identical(extra, tmp_path):
-    need(ODAG); need(REFDEC); need(RM)
+    need(ODAG); need(REFDEC); need(local_data.path("rm1"))
     args = rm_args()
     if "-maxwpf" in extra:
         i = args.index("-maxwpf"); del args[i:i + 2]
@@ -84,7 +86,7 @@ def test_rm1_second_pass_from_the_oracle_is_byte_identical(extra, tmp_path):
 def test_lm_operation_limit_fails_the_same_way(tmp_path):
     """-maxlpf 5: dag_bestpath gives up after 5 x nfrm LM operations ("Bestpath search failed"): the reference then writes
     NO line for the utterance; utterances whose search needs fewer operations write theirs"""
-    need(ODAG); need(REFDEC); need(RM)
+    need(ODAG); need(REFDEC); need(local_data.path("rm1"))
     out = both(rm_args(8) + ["-bestpath", "1", "-maxlpf", "5"], tmp_path)
     assert out["odag"][0] == out["ref"][0] and out["odag"][1] == out["ref"][1]
     assert 0 < out["ref"][0].count("\n") < 8

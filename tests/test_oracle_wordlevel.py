@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import oracle_wordlevel as OW
+import local_data
 import wordlevel_trace as WT
 from conftest import GOLDEN, ROOT
 
@@ -53,7 +54,7 @@ def test_reference_decoder_with_oracle_word_level_is_byte_identical(name, extra,
 
 @pytest.mark.parametrize("extra", [[], ["-maxwpf", "3", "-maxhistpf", "8", "-bghist", "1"]])
 def test_rm1_with_oracle_word_level_is_byte_identical(extra, tmp_path):
-    need(OWL); need(REFDEC); need(RM)
+    need(OWL); need(REFDEC); need(local_data.path("rm1"))
     args = ["-mdef", f"{RM}/mdef", "-fdict", f"{RM}/fillerdict", "-dict", f"{RM}/RM.dictionary", "-mean", f"{RM}/means",
             "-var", f"{RM}/variances", "-mixw", f"{RM}/mixture_weights", "-tmat", f"{RM}/transition_matrices",
             "-agc", "none", "-varnorm", "no", "-cmn", "current", "-epl", "4", "-fillprob", "0.02", "-maxwpf", "10",
