@@ -44,6 +44,8 @@
 #include "s3a_wordlevel.h"
 #include "s3a_lm3g.h"
 #include "s3a_dag.h"
+#define S3A_HOSTMEM_WHO "s3a_utt"
+#include "s3a_hostmem.h"
 
 /* A pointer that came out of a structure in memory is a GENERIC pointer to the compiler; what it makes of an access through one is
  * flat_load / flat_store -- counted by the LDS counter as well as the memory counter, so that every wait for an LDS read waits for
@@ -3166,9 +3168,9 @@ ku_fill32(int32_t *p, int32_t v, size_t n)
 /* host side                                                           */
 /* ------------------------------------------------------------------ */
 
-#define DM(ptr, bytes) do { if (hipMalloc((void **)&(ptr), (bytes) > 0 ? (bytes) : 4) != hipSuccess) { \
-        s3a_set_error("s3a_utt: device allocation of %zu bytes failed", (size_t)(bytes)); goto fail; } } while (0)
-#define UPV(dst, vec) do { DM(dst, (vec).size() * 4); \
+/* (own: the s3a_hostmem that records the allocation and frees it) */
+#define DM(own, ptr, bytes) do { if (!(own).dev(ptr, bytes)) goto fail; } while (0)
+#define UPV(own, dst, vec) do { DM(own, dst, (vec).size() * 4); \
         if ((vec).size() && hipMemcpy((void *)(dst), (vec).data(), (vec).size() * 4, hipMemcpyHostToDevice) != hipSuccess) { \
             s3a_set_error("s3a_utt: upload failed"); goto fail; } } while (0)
 
@@ -3230,13 +3232,16 @@ s3a_lm3g_init(int32_t n_ug, const int32_t *ug_prob, const int32_t *ug_bowt, cons
 {
     s3a_lm3g_t *lm = lm3g_host(n_ug, ug_prob, ug_bowt, ug_firstbg, n_bg, bg_wid, bg_prob, bg_bowt, bg_firsttg, n_tg, tg_wid, tg_prob, inclass_ugscore, n_dictword);
     if (!lm) return NULL;
-    UPV(lm->d.ug_prob, lm->ug_prob); UPV(lm->d.ug_bowt, lm->ug_bowt); UPV(lm->d.ug_firstbg, lm->ug_firstbg);
-    UPV(lm->d.bg_wid, lm->bg_wid); UPV(lm->d.bg_prob, lm->bg_prob); UPV(lm->d.bg_bowt, lm->bg_bowt);
-    UPV(lm->d.bg_firsttg, lm->bg_firsttg); UPV(lm->d.tg_wid, lm->tg_wid); UPV(lm->d.tg_prob, lm->tg_prob);
-    if (inclass_ugscore) UPV(lm->d.inclass, lm->inclass);
+    s3a_hostmem own;
+    UPV(own, lm->d.ug_prob, lm->ug_prob); UPV(own, lm->d.ug_bowt, lm->ug_bowt); UPV(own, lm->d.ug_firstbg, lm->ug_firstbg);
+    UPV(own, lm->d.bg_wid, lm->bg_wid); UPV(own, lm->d.bg_prob, lm->bg_prob); UPV(own, lm->d.bg_bowt, lm->bg_bowt);
+    UPV(own, lm->d.bg_firsttg, lm->bg_firsttg); UPV(own, lm->d.tg_wid, lm->tg_wid); UPV(own, lm->d.tg_prob, lm->tg_prob);
+    if (inclass_ugscore) UPV(own, lm->d.inclass, lm->inclass);
+    own.recs.clear();           /* (the handle's from here on: s3a_lm3g_free) */
     return lm;
 fail:
-    s3a_lm3g_free(lm);
+    own.free_all();
+    delete lm;
     return NULL;
 }
 
@@ -3332,17 +3337,14 @@ struct HostLane {
     s3a_scorer_t *sc;
     ULane d;
     UCtx *h_ctx;                /* pinned */
-    float *d_feat;
-    size_t feat_cap;
-    float *h_feat;              /* pinned staging */
-    size_t h_feat_cap;
-    int32_t *h_tab;             /* pinned: the downloaded history table [13 arrays] */
-    size_t h_tab_cap;
+    s3a_grow<float> feat_d, feat_h;     /* the utterance's features: device / pinned staging */
+    s3a_grow<int32_t> tab;      /* pinned: the downloaded history table [13 arrays] */
     int32_t *h_st, *h_fstat;    /* pinned */
     int32_t nfr, n_entry, epoch, dirty;
 };
 
 struct s3a_uttdec_s {
+    s3a_hostmem mem;            /* every device / pinned buffer below is its: s3a_uttdec_free frees them through it */
     s3a_lm3g_t *lm;
     s3a_comsen_t *cs;
     s3a_mgau_model_t *g;
@@ -3394,13 +3396,13 @@ struct s3a_uttdec_s {
     /* s3a_uttdec_decode_queue (lane refill): everything of a queue lives in buffers that only grow */
     int32_t q_n;                /* utterances of the last decode when it was a queue (0: a plain decode) */
     std::vector<int32_t> q_nfr; /* their frame counts */
-    float *q_feat_d, *q_feat_h; size_t q_feat_cap;      /* the queue's features, rows padded to the scorer's stride */
-    UCtx *q_ctx_d, *q_ctx_h; size_t q_ctx_cap;          /* the utterances' staged contexts */
-    int32_t *q_sched_d, *q_sched_h; size_t q_sched_cap; /* the refill events' lane / utterance lists */
-    int32_t *q_hdr_d, *q_hdr_h; size_t q_hdr_cap;       /* [n_utt][UH_N] + the word counter */
-    int32_t *q_words_d, *q_words_h; size_t q_words_cap, q_words_hcap;   /* hypothesis words, packed (6 int32 each) */
-    int32_t *q_dio_d, *q_dio_h; size_t q_dio_cap;       /* the second pass inside a queue: [n_utt][DG_IO_N] + the word counter */
-    int32_t *q_dw_d, *q_dw_h; size_t q_dw_cap, q_dw_hcap;   /* its words, packed */
+    s3a_grow<float> q_feat;     /* the queue's features, rows padded to the scorer's stride */
+    s3a_grow<UCtx> q_ctx;       /* the utterances' staged contexts */
+    s3a_grow<int32_t> q_sched;  /* the refill events' lane / utterance lists */
+    s3a_grow<int32_t> q_hdr;    /* [n_utt][UH_N] + the word counter */
+    s3a_grow<int32_t> q_words, q_words_pin;     /* hypothesis words, packed (6 int32 each): device | pinned, sized by what came out */
+    s3a_grow<int32_t> q_dio;    /* the second pass inside a queue: [n_utt][DG_IO_N] + the word counter */
+    s3a_grow<int32_t> q_dw, q_dw_pin;           /* its words, packed */
     int32_t q_dag;              /* the last queue ran the second pass */
     int32_t q_keep_lat;         /* s3a_uttdec_queue_keep_lattices: the queue's lattices are read back group by group (event by event) */
     struct QLat { s3a_lat_info_t info; std::vector<s3a_lat_node_t> nodes; std::vector<s3a_lat_link_t> links; int32_t have; };
@@ -3416,14 +3418,14 @@ struct s3a_uttdec_s {
     void *d_kfargs, *h_kfargs;  /* [KF_ARG_SLOTS] KfArgs: ku_frames' shared arguments (device / pinned) */
     int32_t kf_arg_at;
     /* SCORES FIRST: every frame's senone scores of a call (ku_frames, KF_STATIC / KF_QUEUE) */
-    int32_t *sb_scores; uint8_t *sb_bests; size_t sb_rows_cap;
+    s3a_grow<int32_t> sb_scores; s3a_grow<uint8_t> sb_bests;    /* (capacity in rows of n_sen; both grow together: sb_reserve) */
     size_t sb_rows_max;         /* s3a_uttdec_opts_t.score_rows_max: a cap on the buffer's rows (0: half of the free device memory) */
-    int32_t *kf_order_d, *kf_order_h; size_t kf_order_cap;      /* KF_QUEUE: the order in which the lanes take the queue's utterances (longest first) */
+    s3a_grow<int32_t> kf_order; /* KF_QUEUE: the order in which the lanes take the queue's utterances (longest first) */
     int32_t kf_shared;          /* another PROCESS holds this device's cluster lock: this engine's lanes stay one workgroup each */
     int32_t *d_kfrelay;         /* [(KF_STAGES + 1) (KF_ST_WORDS + n_lanes) + 3 n_lanes] the relay's words per launch of the chain | lane_f | lane_uq | lane_stop */
     int32_t kf_n_relay;         /* launches the last call's chain had behind its first (diagnostics) */
-    UwGroup *sb_gdesc_d, *sb_gdesc_h; size_t sb_g_cap;
-    long long *sb_row0_d, *sb_row0_h; size_t sb_row0_cap;
+    s3a_grow<UwGroup> sb_gdesc;
+    s3a_grow<long long> sb_row0;
     /* where the last call's device time went: events around the scoring launches and around ku_frames (s3a_uttdec_last_parts) */
     std::vector<hipEvent_t> kf_evs;
     int32_t kf_ev_n, kf_n_score, kf_n_frames;
@@ -3475,47 +3477,36 @@ fill32(hipStream_t st, int32_t *p, int32_t v, size_t n)
     return S3A_OK;
 }
 
-static void
-wlane_free(WLane &w)
-{
-    void *p[] = { w.score, w.pred, w.lw0, w.lw1, w.wid, w.sf, w.ef, w.ascr, w.lscr, w.type, w.lmc, w.frame_start, w.bestscore,
-                  w.bestvh, w.st, w.ex_off, w.ex_info, w.cand_i, w.cand_pref, w.cand_e, w.cand_score, w.cand_slot, w.hkey, w.hbest, w.hfirst,
-                  w.hlead_rank, w.sg, w.srt, w.wfirst, w.wbest, w.part, w.part2, w.tb, w.heap, w.nrl, w.fstat };
-    for (auto q : p) if (q) (void)hipFree(q);
-    memset((void *)&w, 0, sizeof w);
-}
-
-/* one lane's history table and per-frame scratch */
+/* one lane's history table and per-frame scratch (own frees them: a failure leaves what was allocated to the owner's free_all) */
 static int32_t
-wlane_alloc(WLane &w, int32_t vh_cap, int32_t max_frames, int32_t ex_cap, int32_t cand_cap, int32_t new_cap, int32_t n_word,
+wlane_alloc(s3a_hostmem &own, WLane &w, int32_t vh_cap, int32_t max_frames, int32_t ex_cap, int32_t cand_cap, int32_t new_cap, int32_t n_word,
             hipStream_t st)
 {
     const size_t vc = (size_t)vh_cap * 4, mf = (size_t)(max_frames + 2) * 4;
     size_t hs = 1024;
     memset((void *)&w, 0, sizeof w);
-    DM(w.score, vc); DM(w.pred, vc); DM(w.lw0, vc); DM(w.lw1, vc); DM(w.wid, vc); DM(w.sf, vc); DM(w.ef, vc);
-    DM(w.ascr, vc); DM(w.lscr, vc); DM(w.type, vc); DM(w.lmc, 5 * vc);
+    DM(own, w.score, vc); DM(own, w.pred, vc); DM(own, w.lw0, vc); DM(own, w.lw1, vc); DM(own, w.wid, vc); DM(own, w.sf, vc); DM(own, w.ef, vc);
+    DM(own, w.ascr, vc); DM(own, w.lscr, vc); DM(own, w.type, vc); DM(own, w.lmc, 5 * vc);
     w.cap = vh_cap;
-    DM(w.frame_start, mf); DM(w.bestscore, mf); DM(w.bestvh, mf); DM(w.st, 16 * 4);
-    DM(w.ex_off, (size_t)(ex_cap + 1) * 4); DM(w.ex_info, (size_t)3 * ex_cap * 4);
+    DM(own, w.frame_start, mf); DM(own, w.bestscore, mf); DM(own, w.bestvh, mf); DM(own, w.st, 16 * 4);
+    DM(own, w.ex_off, (size_t)(ex_cap + 1) * 4); DM(own, w.ex_info, (size_t)3 * ex_cap * 4);
     w.ex_cap = ex_cap;
-    DM(w.cand_score, (size_t)cand_cap * 4); DM(w.cand_slot, (size_t)cand_cap * 4);
-    DM(w.cand_pref, (size_t)cand_cap * 4); DM(w.cand_e, (size_t)cand_cap * 4); DM(w.cand_i, (size_t)cand_cap * 4);
+    DM(own, w.cand_score, (size_t)cand_cap * 4); DM(own, w.cand_slot, (size_t)cand_cap * 4);
+    DM(own, w.cand_pref, (size_t)cand_cap * 4); DM(own, w.cand_e, (size_t)cand_cap * 4); DM(own, w.cand_i, (size_t)cand_cap * 4);
     w.cand_cap = cand_cap;
     while (hs < (size_t)2 * cand_cap) hs <<= 1;
     w.hmask = (int32_t)(hs - 1);
-    DM(w.hkey, hs * 8); DM(w.hbest, hs * 8); DM(w.hfirst, hs * 4); DM(w.hlead_rank, hs * 4);
+    DM(own, w.hkey, hs * 8); DM(own, w.hbest, hs * 8); DM(own, w.hfirst, hs * 4); DM(own, w.hlead_rank, hs * 4);
     if (hipMemset(w.hkey, 0, hs * 8) != hipSuccess || hipMemset(w.hbest, 0, hs * 8) != hipSuccess
         || hipMemset(w.hfirst, 0xff, hs * 4) != hipSuccess) { s3a_set_error("s3a_utt: memset failed"); goto fail; }
     w.new_cap = new_cap;
-    DM(w.sg, (size_t)11 * new_cap * 4); DM(w.srt, (size_t)6 * new_cap * 4); DM(w.heap, (size_t)18 * new_cap * 4); DM(w.nrl, (size_t)new_cap * 4);
-    DM(w.wfirst, (size_t)n_word * 4); DM(w.wbest, (size_t)n_word * 4);
-    DM(w.part, WL_BIG_G * 4); DM(w.part2, WL_BIG_G * 4); DM(w.tb, (WL_MAXT + 1) * 4);
-    DM(w.fstat, (size_t)max_frames * 8 * 4);
+    DM(own, w.sg, (size_t)11 * new_cap * 4); DM(own, w.srt, (size_t)6 * new_cap * 4); DM(own, w.heap, (size_t)18 * new_cap * 4); DM(own, w.nrl, (size_t)new_cap * 4);
+    DM(own, w.wfirst, (size_t)n_word * 4); DM(own, w.wbest, (size_t)n_word * 4);
+    DM(own, w.part, WL_BIG_G * 4); DM(own, w.part2, WL_BIG_G * 4); DM(own, w.tb, (WL_MAXT + 1) * 4);
+    DM(own, w.fstat, (size_t)max_frames * 8 * 4);
     if (fill32(st, w.wfirst, INT_MAX, n_word) != S3A_OK || fill32(st, w.wbest, INT_MIN, n_word) != S3A_OK) goto fail;
     return S3A_OK;
 fail:
-    wlane_free(w);
     return S3A_ENOMEM;
 }
 
@@ -3526,87 +3517,20 @@ s3a_uttdec_free(s3a_uttdec_t *ud)
     (void)hipSetDevice(ud->device);
     (void)hipStreamSynchronize(ud->stream);
     for (auto &hl : ud->lane) {
-        wlane_free(hl.d.w);
-        if (hl.d.pack) (void)hipFree(hl.d.pack);
-        if (hl.d.cs_need) (void)hipFree(hl.d.cs_need);
-        if (hl.d.cs_val) (void)hipFree(hl.d.cs_val);
-        if (hl.d.cs_wl) (void)hipFree(hl.d.cs_wl);
-        if (hl.d.cs_wn) (void)hipFree(hl.d.cs_wn);
-        if (hl.d.posbest) (void)hipFree(hl.d.posbest);
-        if (hl.d.posps) (void)hipFree(hl.d.posps);
-        if (hl.d.senbits) (void)hipFree(hl.d.senbits);
-        if (hl.d.dynbeam) (void)hipFree(hl.d.dynbeam);
-        if (hl.d.pstamp8) (void)hipFree(hl.d.pstamp8);
-        if (hl.d.plist) (void)hipFree(hl.d.plist);
-        if (hl.d.claim) (void)hipFree(hl.d.claim);
-        if (hl.d.pcnt) (void)hipFree(hl.d.pcnt);
-        if (hl.d.ci_all) (void)hipFree(hl.d.ci_all);
-        if (hl.d.heur_all) (void)hipFree(hl.d.heur_all);
-        if (hl.d.hth_pos) (void)hipFree(hl.d.hth_pos);
-        if (hl.d.ph_scratch) (void)hipFree(hl.d.ph_scratch);
-        if (hl.d.win) (void)hipFree(hl.d.win);
-        if (hl.d.winb) (void)hipFree(hl.d.winb);
         if (hl.ls && ud->S.nact_all && hl.ls->d_nact[0] >= ud->S.nact_all
             && hl.ls->d_nact[0] < ud->S.nact_all + (size_t)ud->n_lanes * 2 * WL_MAXT)
             hl.ls->d_nact[0] = hl.ls->d_nact[1] = NULL;     /* borrowed from nact_all */
-        if (hl.d_feat) (void)hipFree(hl.d_feat);
-        if (hl.h_feat) (void)hipHostFree(hl.h_feat);
-        if (hl.h_tab) (void)hipHostFree(hl.h_tab);
-        if (hl.h_st) (void)hipHostFree(hl.h_st);
-        if (hl.h_fstat) (void)hipHostFree(hl.h_fstat);
         if (hl.sc) s3a_scorer_free(hl.sc);
         if (hl.ls) s3a_lexsearch_free(hl.ls);
     }
     if (ud->kf_counted) { g_kf_live[ud->device]--; ud->kf_counted = 0; kf_device_unlock(ud->device); }
-    if (ud->kf_order_d) (void)hipFree(ud->kf_order_d);
-    if (ud->kf_order_h) (void)hipHostFree(ud->kf_order_h);
     for (auto e : ud->kf_evs) (void)hipEventDestroy(e);
     ud->kf_evs.clear();
-    if (ud->d_kfbar) (void)hipFree(ud->d_kfbar);
-    if (ud->d_kfrelay) (void)hipFree(ud->d_kfrelay);
-    if (ud->d_kfnext) (void)hipFree(ud->d_kfnext);
-    if (ud->d_kfargs) (void)hipFree(ud->d_kfargs);
-    if (ud->h_kfargs) (void)hipHostFree(ud->h_kfargs);
-    if (ud->sb_scores) (void)hipFree(ud->sb_scores);
-    if (ud->sb_bests) (void)hipFree(ud->sb_bests);
-    if (ud->sb_gdesc_d) (void)hipFree(ud->sb_gdesc_d);
-    if (ud->sb_gdesc_h) (void)hipHostFree(ud->sb_gdesc_h);
-    if (ud->sb_row0_d) (void)hipFree(ud->sb_row0_d);
-    if (ud->sb_row0_h) (void)hipHostFree(ud->sb_row0_h);
-    if (ud->q_dio_d) (void)hipFree(ud->q_dio_d);
-    if (ud->q_dio_h) (void)hipHostFree(ud->q_dio_h);
-    if (ud->q_dw_d) (void)hipFree(ud->q_dw_d);
-    if (ud->q_dw_h) (void)hipHostFree(ud->q_dw_h);
     if (ud->dag) s3a_dagpass_free(ud->dag);
-    {
-        void *qd[] = { ud->q_feat_d, ud->q_ctx_d, ud->q_sched_d, ud->q_hdr_d, ud->q_words_d };
-        void *qh[] = { ud->q_feat_h, ud->q_ctx_h, ud->q_sched_h, ud->q_hdr_h, ud->q_words_h };
-        for (auto q : qd) if (q) (void)hipFree(q);
-        for (auto q : qh) if (q) (void)hipHostFree(q);
-    }
     for (auto &fg_ : ud->graphs) if (fg_.exec) (void)hipGraphExecDestroy(fg_.exec);
-    if (ud->d_fgbase) (void)hipFree(ud->d_fgbase);
-    if (ud->h_ctx_up) (void)hipHostFree(ud->h_ctx_up);
-    if (ud->h_ctx_dn) (void)hipHostFree(ud->h_ctx_dn);
-    if (ud->h_hyp_hdr) (void)hipHostFree(ud->h_hyp_hdr);
-    if (ud->h_hyp_words) (void)hipHostFree(ud->h_hyp_words);
-    if (ud->d_hyp_hdr) (void)hipFree(ud->d_hyp_hdr);
-    if (ud->d_hyp_words) (void)hipFree(ud->d_hyp_words);
     if (ud->ev0) (void)hipEventDestroy(ud->ev0);
     if (ud->ev1) (void)hipEventDestroy(ud->ev1);
-    if (ud->d_lanes) (void)hipFree(ud->d_lanes);
-    if (ud->S.node_ci) (void)hipFree((void *)ud->S.node_ci);
-    if (ud->S.sen2cimap) (void)hipFree((void *)ud->S.sen2cimap);
-    if (ud->S.rootprob) (void)hipFree((void *)ud->S.rootprob);
-    if (ud->S.pshdr) (void)hipFree((void *)ud->S.pshdr);
-    if (ud->S.node4) (void)hipFree((void *)ud->S.node4);
-    if (ud->S.nodesen) (void)hipFree((void *)ud->S.nodesen);
-    if (ud->S.nodepk) (void)hipFree((void *)ud->S.nodepk);
-    if (ud->S.ctx_all) (void)hipFree(ud->S.ctx_all);
-    if (ud->S.nact_all) (void)hipFree(ud->S.nact_all);
-    if (ud->d_lcmap) (void)hipFree(ud->d_lcmap);
-    const void *q[] = { ud->dict.lwid, ud->dict.fillpen, ud->dict.last_ci, ud->dict.is_filler };
-    for (auto p : q) if (p) (void)hipFree((void *)p);
+    ud->mem.free_all();         /* every buffer of the engine and its lanes */
     delete ud;
 }
 
@@ -3673,11 +3597,10 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
         s3a_set_error("s3a_uttdec_init: the LM's class table and the dictionary disagree");
         return NULL;
     }
-    s3a_uttdec_t *ud = new s3a_uttdec_s();
+    s3a_uttdec_t *ud = new s3a_uttdec_s();      /* (value-initialised: every member not set below is 0 / NULL -- relied on) */
     ud->lm = lm; ud->cs = cs; ud->g = g; ud->n_lanes = n_lanes; ud->max_frames = max_frames;
     ud->cfg = *cfg;
-    ud->d_lanes = NULL; ud->d_lcmap = NULL; ud->n_utt = 0; ud->last_decode_ms = 0.0; ud->prof_every = 0;
-    ud->device = 0; ud->ev0 = ud->ev1 = NULL; ud->dag = NULL; ud->keep_tables = 1; ud->tables_fetched = 0; ud->use_graph = 0; ud->d_fgbase = NULL; ud->q_n = 0; ud->q_feat_d = ud->q_feat_h = NULL; ud->q_ctx_d = ud->q_ctx_h = NULL; ud->q_sched_d = ud->q_sched_h = NULL; ud->q_hdr_d = ud->q_hdr_h = NULL; ud->q_words_d = ud->q_words_h = NULL; ud->q_dio_d = ud->q_dio_h = NULL; ud->q_dw_d = ud->q_dw_h = NULL; ud->q_dio_cap = ud->q_dw_cap = ud->q_dw_hcap = 0; ud->q_dag = 0; ud->q_keep_lat = 0; ud->q_feat_cap = ud->q_ctx_cap = ud->q_sched_cap = ud->q_hdr_cap = ud->q_words_cap = ud->q_words_hcap = 0; ud->h_ctx_up = NULL; ud->h_ctx_dn = NULL; ud->d_hyp_hdr = ud->h_hyp_hdr = ud->d_hyp_words = ud->h_hyp_words = NULL; ud->hyp_wcap = 0; ud->n_pset = proto->n_pset;
+    ud->keep_tables = 1; ud->n_pset = proto->n_pset;
     (void)hipGetDevice(&ud->device);
     memset(ud->prof_us, 0, sizeof ud->prof_us); memset(ud->prof_n, 0, sizeof ud->prof_n);
     memset(&ud->dict, 0, sizeof ud->dict);
@@ -3700,19 +3623,19 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
     S.par = proto->d_par; S.tree_of = proto->d_tree_of; S.rootlist = proto->d_rootlist; S.tp = proto->d_tp; S.ne = proto->n_emit;
     {   /* the nodes' static words, packed */
         int4 *n4 = NULL;
-        if (hipMalloc((void **)&n4, (size_t)(proto->N > 0 ? proto->N : 1) * sizeof(int4)) != hipSuccess) { s3a_set_error("s3a_uttdec_init: out of device memory"); goto fail; }
+        if (!ud->mem.dev(n4, (size_t)(proto->N > 0 ? proto->N : 1) * sizeof(int4))) { s3a_set_error("s3a_uttdec_init: out of device memory"); goto fail; }
         hipLaunchKernelGGL(ku_pack_node4, dim3((unsigned)((proto->N + 255) / 256)), dim3(256), 0, ud->stream, proto->d_ssid, proto->d_tmatid,
                            proto->d_wid, proto->d_comp, n4, proto->N);
         S.node4 = n4;
         int32_t *ns = NULL;
         const int32_t ne = proto->n_emit;
-        DM(ns, (size_t)proto->N * (ne == 3 ? 2 : 4) * 4);
+        DM(ud->mem, ns, (size_t)proto->N * (ne == 3 ? 2 : 4) * 4);
         S.nodesen = ns;
         hipLaunchKernelGGL(ku_pack_nodesen, dim3((unsigned)((proto->N + 255) / 256)), dim3(256), 0, ud->stream, proto->d_ssid, proto->d_comp, proto->d_sseq,
                            proto->d_comsseq, ns, proto->N, ne);
         if (ne == 3 && proto->n_tmat < 65536 && proto->d_ps && proto->N < (1 << 28)) {
             int4 *pk = NULL;
-            DM(pk, (size_t)(proto->N > 0 ? proto->N : 1) * sizeof(int4));
+            DM(ud->mem, pk, (size_t)(proto->N > 0 ? proto->N : 1) * sizeof(int4));
             S.nodepk = pk;
             hipLaunchKernelGGL(ku_pack_nodepk, dim3((unsigned)((proto->N + 255) / 256)), dim3(256), 0, ud->stream, proto->d_ssid, proto->d_tmatid, proto->d_wid,
                                proto->d_comp, proto->d_sseq, proto->d_comsseq, proto->d_ps, proto->d_par_off, pk, proto->N);
@@ -3721,7 +3644,7 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
     S.pshdr = NULL;
     if (proto->d_ps && proto->n_pset > 0) {
         int4 *ph = NULL;
-        if (hipMalloc((void **)&ph, (size_t)proto->n_pset * sizeof(int4)) != hipSuccess) { s3a_set_error("s3a_uttdec_init: out of device memory"); goto fail; }
+        if (!ud->mem.dev(ph, (size_t)proto->n_pset * sizeof(int4))) { s3a_set_error("s3a_uttdec_init: out of device memory"); goto fail; }
         hipLaunchKernelGGL(ku_pack_pshdr, dim3((unsigned)((proto->n_pset + 255) / 256)), dim3(256), 0, ud->stream, proto->d_psmem_off, proto->d_psmem, proto->d_par_off,
                            ph, proto->n_pset);
         S.pshdr = ph;
@@ -3730,7 +3653,7 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
         const size_t nr = proto->h_rootlist.size();
         int32_t *rp = NULL;
         if (nr > 0) {
-            if (hipMalloc((void **)&rp, nr * 4) != hipSuccess) { s3a_set_error("s3a_uttdec_init: out of device memory"); goto fail; }
+            if (!ud->mem.dev(rp, nr * 4)) { s3a_set_error("s3a_uttdec_init: out of device memory"); goto fail; }
             hipLaunchKernelGGL(ku_gather32, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, ud->stream, proto->d_prob, proto->d_rootlist, rp, nr);
         }
         S.rootprob = rp;
@@ -3748,8 +3671,7 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
     /* launch geometry: fixed grids, the kernels loop over the list lengths they find in memory */
     ud->eval_block = (cfg->maxhmmpf >= EVBLOCK_LONG_LIST && maxn >= EVBLOCK_LONG_LIST) ? 256 : 64;
     ud->no_multi = O.no_multi != 0;
-    ud->d_dbg = NULL;
-    if (O.framecheck) { if (hipMalloc((void **)&ud->d_dbg, (size_t)n_lanes * 64) != hipSuccess || hipMemset(ud->d_dbg, 0, (size_t)n_lanes * 64) != hipSuccess) ud->d_dbg = NULL; }
+    if (O.framecheck && (!ud->mem.dev(ud->d_dbg, (size_t)n_lanes * 64) || hipMemset(ud->d_dbg, 0, (size_t)n_lanes * 64) != hipSuccess)) ud->d_dbg = NULL;
     ud->gy = O.gy;
     ud->many = O.many > 0 ? O.many : 32;
     /* fixed grids, sized for the usual frame: a workgroup loops when a list is longer (virtual workgroups); with many
@@ -3827,7 +3749,7 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
     {
         int32_t *p0 = NULL, *p1 = NULL, *p2 = NULL;
         uint8_t *p3 = NULL;
-        DM(p0, (size_t)cfg->n_word * 4); DM(p1, (size_t)cfg->n_word * 4); DM(p2, (size_t)cfg->n_word * 4); DM(p3, (size_t)cfg->n_word);
+        DM(ud->mem, p0, (size_t)cfg->n_word * 4); DM(ud->mem, p1, (size_t)cfg->n_word * 4); DM(ud->mem, p2, (size_t)cfg->n_word * 4); DM(ud->mem, p3, (size_t)cfg->n_word);
         ud->dict.lwid = p0; ud->dict.fillpen = p1; ud->dict.last_ci = p2; ud->dict.is_filler = p3;
         ud->dict.n_word = cfg->n_word; ud->dict.n_ci = cfg->n_ci;
         if (hipMemcpy(p0, cfg->lwid, (size_t)cfg->n_word * 4, hipMemcpyHostToDevice) != hipSuccess
@@ -3837,7 +3759,7 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
             s3a_set_error("s3a_uttdec_init: upload failed");
             goto fail;
         }
-        UPV(ud->d_lcmap, ud->h_lcmap);
+        UPV(ud->mem, ud->d_lcmap, ud->h_lcmap);
     }
     {
         WPar &P = ud->par;
@@ -3867,37 +3789,31 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
     ud->lane.resize(n_lanes);
     for (auto &hl : ud->lane) memset((void *)&hl, 0, sizeof hl);
     if (T > WL_MAXT) { s3a_set_error("s3a_uttdec_init: more than %d lextrees", WL_MAXT); goto fail; }
-    DM(ud->S.ctx_all, sizeof(UCtx) * n_lanes);
-    DM(ud->S.nact_all, (size_t)n_lanes * 2 * WL_MAXT * 4);
-    DM(ud->d_fgbase, 64);
+    DM(ud->mem, ud->S.ctx_all, sizeof(UCtx) * n_lanes);
+    DM(ud->mem, ud->S.nact_all, (size_t)n_lanes * 2 * WL_MAXT * 4);
+    DM(ud->mem, ud->d_fgbase, 64);
     if (hipMemset(ud->d_fgbase, 0, 64) != hipSuccess) goto fail;
     ud->S.fgbase = ud->d_fgbase;
     ud->use_graph = O.graph != 0 && !ud->big_wl && !O.framecheck;
     ud->persist = O.persist >= 0 && !ud->use_graph && !O.framecheck ? (O.persist > 1 ? 3 : O.persist > 0 ? 2 : 1) : 0;     /* (2: whatever the lane count; 3: and with the general barrier only) */
-    ud->kf_cluster_opt = O.cluster; ud->kf_last_c = 0; ud->kf_slots = 0; ud->d_kfbar = NULL; ud->kf_counted = 0; ud->d_kfnext = NULL; ud->d_kfargs = ud->h_kfargs = NULL; ud->kf_arg_at = 0;
-    ud->sb_scores = NULL; ud->sb_bests = NULL; ud->sb_rows_cap = 0; ud->sb_gdesc_d = ud->sb_gdesc_h = NULL; ud->sb_g_cap = 0;
-    ud->sb_rows_max = O.score_rows_max > 0 ? (size_t)O.score_rows_max : 0; ud->kf_order_d = ud->kf_order_h = NULL; ud->kf_order_cap = 0; ud->kf_shared = 0;
-    ud->d_kfrelay = NULL; ud->kf_n_relay = 0;
-    ud->sb_row0_d = ud->sb_row0_h = NULL; ud->sb_row0_cap = 0;
-    ud->kf_ev_n = ud->kf_n_score = ud->kf_n_frames = 0; ud->kf_score_ms = ud->kf_frames_ms = 0.0;
+    ud->kf_cluster_opt = O.cluster;
+    ud->sb_rows_max = O.score_rows_max > 0 ? (size_t)O.score_rows_max : 0;
     if (ud->persist) {
-        DM(ud->d_kfnext, (size_t)(16 + n_lanes) * 4);
-        DM(ud->d_kfargs, sizeof(KfArgs) * KF_ARG_SLOTS);
-        if (hipHostMalloc(&ud->h_kfargs, sizeof(KfArgs) * KF_ARG_SLOTS) != hipSuccess) { s3a_set_error("s3a_uttdec_init: pinned allocation failed"); goto fail; }
-        DM(ud->d_kfbar, (size_t)n_lanes * 8);
+        DM(ud->mem, ud->d_kfnext, (size_t)(16 + n_lanes) * 4);
+        DM(ud->mem, ud->d_kfargs, sizeof(KfArgs) * KF_ARG_SLOTS);
+        if (!ud->mem.pin(ud->h_kfargs, sizeof(KfArgs) * KF_ARG_SLOTS)) { s3a_set_error("s3a_uttdec_init: pinned allocation failed"); goto fail; }
+        DM(ud->mem, ud->d_kfbar, (size_t)n_lanes * 8);
         if (hipMemset(ud->d_kfbar, 0, (size_t)n_lanes * 8) != hipSuccess) goto fail;
-        DM(ud->d_kfrelay, ((size_t)(KF_STAGES + 1) * (KF_ST_WORDS + n_lanes) + (size_t)3 * n_lanes) * 4);
+        DM(ud->mem, ud->d_kfrelay, ((size_t)(KF_STAGES + 1) * (KF_ST_WORDS + n_lanes) + (size_t)3 * n_lanes) * 4);
         if (ud->device >= 0 && ud->device < 64) { g_kf_live[ud->device]++; ud->kf_counted = 1; ud->kf_shared = kf_device_lock(ud->device) ? 0 : 1; }
     }
     ud->scan_small_from = O.scan_small_from > 0 ? O.scan_small_from : 64;
     ud->hyp_wcap = max_frames + 4;
-    if (hipHostMalloc((void **)&ud->h_ctx_up, sizeof(UCtx) * n_lanes) != hipSuccess
-        || hipHostMalloc((void **)&ud->h_ctx_dn, sizeof(UCtx) * n_lanes) != hipSuccess
-        || hipHostMalloc((void **)&ud->h_hyp_hdr, ((size_t)n_lanes * UH_N + 1) * 4) != hipSuccess
-        || hipHostMalloc((void **)&ud->h_hyp_words, (size_t)n_lanes * ud->hyp_wcap * 6 * 4) != hipSuccess) { s3a_set_error("s3a_uttdec_init: pinned allocation failed"); goto fail; }
+    if (!ud->mem.pin(ud->h_ctx_up, sizeof(UCtx) * n_lanes) || !ud->mem.pin(ud->h_ctx_dn, sizeof(UCtx) * n_lanes)
+        || !ud->mem.pin(ud->h_hyp_hdr, ((size_t)n_lanes * UH_N + 1) * 4) || !ud->mem.pin(ud->h_hyp_words, (size_t)n_lanes * ud->hyp_wcap * 6 * 4)) { s3a_set_error("s3a_uttdec_init: pinned allocation failed"); goto fail; }
     memset(ud->h_ctx_dn, 0, sizeof(UCtx) * n_lanes);
-    DM(ud->d_hyp_hdr, ((size_t)n_lanes * UH_N + 1) * 4);
-    DM(ud->d_hyp_words, (size_t)n_lanes * ud->hyp_wcap * 6 * 4);
+    DM(ud->mem, ud->d_hyp_hdr, ((size_t)n_lanes * UH_N + 1) * 4);
+    DM(ud->mem, ud->d_hyp_words, (size_t)n_lanes * ud->hyp_wcap * 6 * 4);
     if (hipMemset(ud->S.nact_all, 0, (size_t)n_lanes * 2 * WL_MAXT * 4) != hipSuccess
         || hipMemset(ud->S.ctx_all, 0, sizeof(UCtx) * n_lanes) != hipSuccess) goto fail;
     for (int32_t z = 0; z < n_lanes; z++) {
@@ -3918,7 +3834,7 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
         u.sc = ls->d_sc; u.hist = ls->d_hist; u.outs = ls->d_outs; u.outh = ls->d_outh; u.bests = ls->d_bests;
         u.frame = ls->d_frame; u.pos = ls->d_pos; u.posf = ls->d_posf; u.act[0] = ls->d_act[0]; u.act[1] = ls->d_act[1];
         /* the clone's list lengths move into the engine's array (borrowed: s3a_uttdec_free takes them back) */
-        (void)hipFree(ls->d_nact[0]); (void)hipFree(ls->d_nact[1]);
+        ud->mem.release(ls->d_nact[0]); ud->mem.release(ls->d_nact[1]);
         ls->d_nact[0] = ud->S.nact_all + ((size_t)z * 2) * WL_MAXT; ls->d_nact[1] = ud->S.nact_all + ((size_t)z * 2 + 1) * WL_MAXT;
         u.nact[0] = ls->d_nact[0]; u.nact[1] = ls->d_nact[1]; u.turn = ls->d_turn; u.selfemit = ls->d_selfemit;
         u.cnt = ls->d_cnt; u.base = ls->d_cand; u.best = ls->d_best; u.exits = ls->d_exit; u.nexit = ls->d_nexit;
@@ -3927,26 +3843,25 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
         u.scan_flag = ls->d_scan_flag; u.scan_agg = ls->d_scan_agg; u.scan_pre = ls->d_scan_pre; u.key = ls->d_key;
         u.sen_act = hl.sc->act_d; u.scr = hl.sc->scr_d; u.misc = hl.sc->misc_d; u.bstidx = hl.sc->bstidx_d;
         u.bstscr = hl.sc->bstscr_d; u.updatetime = hl.sc->updatetime_d; u.gpart = hl.sc->gpart_d;
-        DM(u.cs_need, (size_t)(cs->n_comstate + 1) * 4); DM(u.cs_val, (size_t)(cs->n_comstate + 1) * 4); DM(u.dynbeam, 16);
-        DM(u.cs_wl, (size_t)(cs->n_comstate + 1) * 4); DM(u.cs_wn, 16); u.ent = ls->d_ent; DM(u.posbest, (size_t)(proto->N + 64) * 4); DM(u.posps, (size_t)(proto->N + 64) * 4);
-        DM(u.senbits, KF_SENBITS / 8); if (hipMemset(u.senbits, 0, KF_SENBITS / 8) != hipSuccess) goto fail;
-        if (hipMemset(u.cs_wn, 0, 16) != hipSuccess) goto fail; DM(u.pstamp8, (size_t)proto->n_pset + 64); S.n_pset_bytes = proto->n_pset + 64;
-        DM(u.plist, (size_t)(proto->N + 64) * 4); DM(u.pcnt, 16); DM(u.claim, (size_t)(proto->N + 64) * 4);
+        DM(ud->mem, u.cs_need, (size_t)(cs->n_comstate + 1) * 4); DM(ud->mem, u.cs_val, (size_t)(cs->n_comstate + 1) * 4); DM(ud->mem, u.dynbeam, 16);
+        DM(ud->mem, u.cs_wl, (size_t)(cs->n_comstate + 1) * 4); DM(ud->mem, u.cs_wn, 16); u.ent = ls->d_ent; DM(ud->mem, u.posbest, (size_t)(proto->N + 64) * 4); DM(ud->mem, u.posps, (size_t)(proto->N + 64) * 4);
+        DM(ud->mem, u.senbits, KF_SENBITS / 8); if (hipMemset(u.senbits, 0, KF_SENBITS / 8) != hipSuccess) goto fail;
+        if (hipMemset(u.cs_wn, 0, 16) != hipSuccess) goto fail; DM(ud->mem, u.pstamp8, (size_t)proto->n_pset + 64); S.n_pset_bytes = proto->n_pset + 64;
+        DM(ud->mem, u.plist, (size_t)(proto->N + 64) * 4); DM(ud->mem, u.pcnt, 16); DM(ud->mem, u.claim, (size_t)(proto->N + 64) * 4);
         if (hipMemset(u.pcnt, 0, 16) != hipSuccess) goto fail;
         if (hipMemset(u.pstamp8, 0xff, (size_t)proto->n_pset + 64) != hipSuccess) goto fail;
         if (S.win_K > 0) {
-            DM(u.win, (size_t)S.win_K * n_sen * 4); DM(u.winb, (size_t)S.win_K * n_sen);
+            DM(ud->mem, u.win, (size_t)S.win_K * n_sen * 4); DM(ud->mem, u.winb, (size_t)S.win_K * n_sen);
             /* ku_select fills the first USEL_G columns of gpart[]; the others stay neutral */
             if (fill32(ud->stream, u.gpart, INT_MIN, (size_t)max(S.gp_n, 0)) != S3A_OK
                 || fill32(ud->stream, u.gpart + max(S.gp_n, 0), 0, (size_t)2 * max(S.gp_n, 0)) != S3A_OK) goto fail;
         }
         if (fill32(ud->stream, u.cs_need, -1, (size_t)cs->n_comstate + 1) != S3A_OK) goto fail;
         u.ctx = ud->S.ctx_all + z;
-        DM(u.pack, (size_t)(6 * T + 16 + 3 * proto->pack_max_exits) * 4);
-        if (wlane_alloc(u.w, ud->vh_cap, max_frames, ud->ex_cap, ud->cand_cap, ud->new_cap, cfg->n_word, ud->stream) != S3A_OK) goto fail;
+        DM(ud->mem, u.pack, (size_t)(6 * T + 16 + 3 * proto->pack_max_exits) * 4);
+        if (wlane_alloc(ud->mem, u.w, ud->vh_cap, max_frames, ud->ex_cap, ud->cand_cap, ud->new_cap, cfg->n_word, ud->stream) != S3A_OK) goto fail;
         hl.h_ctx = ud->h_ctx_dn + z;
-        if (hipHostMalloc((void **)&hl.h_st, 16 * 4) != hipSuccess
-            || hipHostMalloc((void **)&hl.h_fstat, (size_t)max_frames * 8 * 4) != hipSuccess) {
+        if (!ud->mem.pin(hl.h_st, 16 * 4) || !ud->mem.pin(hl.h_fstat, (size_t)max_frames * 8 * 4)) {
             s3a_set_error("s3a_uttdec_init: pinned allocation failed");
             goto fail;
         }
@@ -3954,7 +3869,7 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
     {
         std::vector<ULane> tmp(n_lanes);
         for (int32_t z = 0; z < n_lanes; z++) tmp[z] = ud->lane[z].d;
-        DM(ud->d_lanes, sizeof(ULane) * n_lanes);
+        DM(ud->mem, ud->d_lanes, sizeof(ULane) * n_lanes);
         if (hipMemcpy(ud->d_lanes, tmp.data(), sizeof(ULane) * n_lanes, hipMemcpyHostToDevice) != hipSuccess) goto fail;
     }
     if (hipStreamSynchronize(ud->stream) != hipSuccess) goto fail;
@@ -4020,25 +3935,15 @@ lane_begin(s3a_uttdec_t *ud, int32_t z, const float *feat, int32_t nfr, int32_t 
         /* (buffers grow with slack: every hipMalloc / hipHostMalloc / free stalls ALL streams of the device, the other
          * engines' too -- a lane must not pay that each time its utterance is a little longer than the last) */
         const size_t grow = (size_t)min(ud->max_frames, max(nfr + nfr / 2, 1024)) * D4x4;
-        if (need > hl.feat_cap) {
-            if (hl.d_feat) (void)hipFree(hl.d_feat);
-            hl.d_feat = NULL; hl.feat_cap = 0;
-            if (hipMalloc((void **)&hl.d_feat, grow * 4) != hipSuccess) { s3a_set_error("s3a_uttdec_decode: feature buffer"); return S3A_ENOMEM; }
-            hl.feat_cap = grow;
-        }
-        if (need > hl.h_feat_cap) {
-            if (hl.h_feat) (void)hipHostFree(hl.h_feat);
-            hl.h_feat = NULL; hl.h_feat_cap = 0;
-            if (hipHostMalloc((void **)&hl.h_feat, grow * 4) != hipSuccess) { s3a_set_error("s3a_uttdec_decode: pinned feature buffer"); return S3A_ENOMEM; }
-            hl.h_feat_cap = grow;
-        }
+        if (hl.feat_d.reserve(ud->mem, S3A_GROW_DEV, need, grow) != S3A_OK) { s3a_set_error("s3a_uttdec_decode: feature buffer"); return S3A_ENOMEM; }
+        if (hl.feat_h.reserve(ud->mem, S3A_GROW_PIN, need, grow) != S3A_OK) { s3a_set_error("s3a_uttdec_decode: pinned feature buffer"); return S3A_ENOMEM; }
         for (int32_t t = 0; t < nfr; t++) {
-            float *row = hl.h_feat + (size_t)t * D4x4;
+            float *row = hl.feat_h.h + (size_t)t * D4x4;
             memcpy(row, feat + (size_t)t * feat_stride, sizeof(float) * ud->veclen);
             for (int32_t k = ud->veclen; k < D4x4; k++) row[k] = 0.0f;
         }
-        HIPCHK(hipMemcpyAsync(hl.d_feat, hl.h_feat, need * 4, hipMemcpyHostToDevice, ud->stream));
-        d_feat_use = hl.d_feat;
+        HIPCHK(hipMemcpyAsync(hl.feat_d.d, hl.feat_h.h, need * 4, hipMemcpyHostToDevice, ud->stream));
+        d_feat_use = hl.feat_d.d;
     }
     else if (feat_stride != D4x4) {
         s3a_set_error("s3a_uttdec_decode_dev: device features must have rows of %d floats (zero padded)", D4x4);
@@ -4279,21 +4184,15 @@ enqueue_frame(s3a_uttdec_t *ud, int32_t n, int32_t f, bool prof)
     return S3A_OK;
 }
 
+/* the buffers of a call that only grow, with a quarter of slack (sides: S3A_GROW_DEV, S3A_GROW_PIN or both) */
 template <typename TP>
 static int32_t
-q_grow(TP **d, TP **h, size_t *cap, size_t need, const char *what)
+q_reserve(s3a_uttdec_t *ud, s3a_grow<TP> &b, int sides, size_t need, const char *what)
 {
-    if (need <= *cap) return S3A_OK;
     const size_t grow = need + need / 4 + 64;
-    if (*d) (void)hipFree(*d);
-    if (h && *h) (void)hipHostFree(*h);
-    *d = NULL; if (h) *h = NULL; *cap = 0;
-    if (hipMalloc((void **)d, grow * sizeof(TP)) != hipSuccess || (h && hipHostMalloc((void **)h, grow * sizeof(TP)) != hipSuccess)) {
-        s3a_set_error("s3a_uttdec_decode_queue: out of memory (%s, %zu bytes)", what, grow * sizeof(TP));
-        return S3A_ENOMEM;
-    }
-    *cap = grow;
-    return S3A_OK;
+    if (b.reserve(ud->mem, sides, need, grow) == S3A_OK) return S3A_OK;
+    s3a_set_error("s3a_uttdec_decode_queue: out of memory (%s, %zu bytes)", what, grow * sizeof(TP));
+    return S3A_ENOMEM;
 }
 
 /* ---- ku_frames: the frames [fg0, fg0 + nf) of all lanes as ONE launch (behind the look-ahead pass that scores them) ---- */
@@ -4487,7 +4386,7 @@ sb_budget_rows(const s3a_uttdec_t *ud)
 {
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) != hipSuccess) return 0;
-    const size_t per_row = (size_t)ud->S.n_sen * 5, rows = (fr / 2 + ud->sb_rows_cap * per_row) / per_row;
+    const size_t per_row = (size_t)ud->S.n_sen * 5, rows = (fr / 2 + ud->sb_scores.cap * per_row) / per_row;
     return ud->sb_rows_max > 0 ? min(rows, ud->sb_rows_max) : rows;
 }
 
@@ -4495,22 +4394,18 @@ static int32_t
 sb_reserve(s3a_uttdec_t *ud, size_t rows, size_t groups, size_t n_utt)
 {
     const size_t S_ = (size_t)ud->S.n_sen;
-    if (rows > ud->sb_rows_cap) {
-        if (ud->sb_scores) (void)hipFree(ud->sb_scores);
-        if (ud->sb_bests) (void)hipFree(ud->sb_bests);
-        ud->sb_scores = NULL; ud->sb_bests = NULL; ud->sb_rows_cap = 0;
+    if (rows > ud->sb_scores.cap) {         /* (both go before either comes back) */
         const size_t grow = rows + rows / 16 + 64;
-        if (hipMalloc((void **)&ud->sb_scores, grow * S_ * 4) != hipSuccess || hipMalloc((void **)&ud->sb_bests, grow * S_) != hipSuccess) {
-            if (ud->sb_scores) (void)hipFree(ud->sb_scores);
-            ud->sb_scores = NULL; ud->sb_bests = NULL;
+        ud->sb_scores.clear(ud->mem); ud->sb_bests.clear(ud->mem);
+        if (ud->sb_scores.reserve(ud->mem, S3A_GROW_DEV, rows, grow, S_ * 4) != S3A_OK || ud->sb_bests.reserve(ud->mem, S3A_GROW_DEV, rows, grow, S_) != S3A_OK) {
+            ud->sb_scores.clear(ud->mem);
             s3a_set_error("s3a_uttdec: the score buffer (%zu rows of %zu senones) does not fit the device", grow, S_);
             return S3A_ENOMEM;
         }
-        ud->sb_rows_cap = grow;
     }
     int32_t rc;
-    if ((rc = q_grow(&ud->sb_gdesc_d, &ud->sb_gdesc_h, &ud->sb_g_cap, groups, "score groups")) != S3A_OK) return rc;
-    if ((rc = q_grow(&ud->sb_row0_d, &ud->sb_row0_h, &ud->sb_row0_cap, n_utt + 1, "score rows")) != S3A_OK) return rc;
+    if ((rc = q_reserve(ud, ud->sb_gdesc, S3A_GROW_DEV | S3A_GROW_PIN, groups, "score groups")) != S3A_OK) return rc;
+    if ((rc = q_reserve(ud, ud->sb_row0, S3A_GROW_DEV | S3A_GROW_PIN, n_utt + 1, "score rows")) != S3A_OK) return rc;
     return S3A_OK;
 }
 
@@ -4522,12 +4417,12 @@ sb_describe(s3a_uttdec_t *ud, const float *const *feat_dev, const int32_t *n_fra
     const int32_t DP = ud->S.D4 * 4;
     size_t row = 0, g = g_at;
     for (int32_t u = u0; u < u1; u++) {
-        ud->sb_row0_h[u] = (long long)row;
+        ud->sb_row0.h[u] = (long long)row;
         for (int32_t j0 = 0; j0 < n_frames[u]; j0 += UW_FB, g++) {
-            UwGroup &gr = ud->sb_gdesc_h[g];
+            UwGroup &gr = ud->sb_gdesc.h[g];
             gr.feat = feat_dev[u] + (size_t)j0 * DP;
-            gr.win = ud->sb_scores + (row + j0) * S_;
-            gr.winb = ud->sb_bests + (row + j0) * S_;
+            gr.win = ud->sb_scores.d + (row + j0) * S_;
+            gr.winb = ud->sb_bests.d + (row + j0) * S_;
             gr.nv = min(UW_FB, n_frames[u] - j0); gr.pad = 0;
         }
         row += (size_t)n_frames[u];
@@ -4541,10 +4436,28 @@ static int32_t
 sb_score(s3a_uttdec_t *ud, size_t g0, size_t n_g)
 {
     for (size_t g = 0; g < n_g; g += SB_PIECE) {
-        const int32_t rc = uw_launch(ud, 0, 0, false, ud->sb_gdesc_d + g0 + g, (int32_t)min((size_t)SB_PIECE, n_g - g));
+        const int32_t rc = uw_launch(ud, 0, 0, false, ud->sb_gdesc.d + g0 + g, (int32_t)min((size_t)SB_PIECE, n_g - g));
         if (rc != S3A_OK) return rc;
         ud->kf_n_score++;
     }
+    return S3A_OK;
+}
+
+/* lanes 0 .. m - 1 from their first frame to their last: the groups [g0, g0 + n_g) of the uploaded table scored, then ONE chain of ku_frames
+ * launches (KF_STATIC; row0[z]: lane z's first row of scores), with the time marks around both (kf_collect) */
+static int32_t
+kf_static_group(s3a_uttdec_t *ud, int32_t m, const long long *row0, size_t g0, size_t n_g)
+{
+    int32_t rc;
+    kf_mark(ud);
+    if ((rc = sb_score(ud, g0, n_g)) != S3A_OK) return rc;
+    kf_mark(ud);
+    KfJob J;
+    memset(&J, 0, sizeof J);
+    J.mode = KF_STATIC; J.row0 = row0; J.scores = ud->sb_scores.d; J.bests = ud->sb_bests.d;
+    if ((rc = kf_launch_chain(ud, m, J)) != S3A_OK) return rc;
+    ud->kf_n_frames++;
+    kf_mark(ud);
     return S3A_OK;
 }
 
@@ -4560,19 +4473,10 @@ kf_decode_static(s3a_uttdec_t *ud, int32_t n_utt, const int32_t *n_frames)
     int32_t rc;
     if ((rc = sb_reserve(ud, rows, groups, (size_t)n_utt)) != S3A_OK) return rc;
     const size_t ng = sb_describe(ud, fd.data(), n_frames, 0, n_utt, 0);
-    HIPCHK(hipMemcpyAsync(ud->sb_gdesc_d, ud->sb_gdesc_h, ng * sizeof(UwGroup), hipMemcpyHostToDevice, ud->stream));
-    HIPCHK(hipMemcpyAsync(ud->sb_row0_d, ud->sb_row0_h, (size_t)n_utt * 8, hipMemcpyHostToDevice, ud->stream));
+    HIPCHK(hipMemcpyAsync(ud->sb_gdesc.d, ud->sb_gdesc.h, ng * sizeof(UwGroup), hipMemcpyHostToDevice, ud->stream));
+    HIPCHK(hipMemcpyAsync(ud->sb_row0.d, ud->sb_row0.h, (size_t)n_utt * 8, hipMemcpyHostToDevice, ud->stream));
     ud->kf_n_score = ud->kf_n_frames = 0;
-    kf_mark(ud);
-    if ((rc = sb_score(ud, 0, ng)) != S3A_OK) return rc;
-    kf_mark(ud);
-    KfJob J;
-    memset(&J, 0, sizeof J);
-    J.mode = KF_STATIC; J.row0 = ud->sb_row0_d; J.scores = ud->sb_scores; J.bests = ud->sb_bests;
-    rc = kf_launch_chain(ud, n_utt, J);
-    ud->kf_n_frames++;
-    kf_mark(ud);
-    return rc;
+    return kf_static_group(ud, n_utt, ud->sb_row0.d, 0, ng);
 }
 
 /* s3a_uttdec_decode_queue through ku_frames: the lanes take the utterances themselves.  The queue goes through in as many parts as
@@ -4597,17 +4501,17 @@ kf_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat_dev, c
     if ((rc = sb_reserve(ud, max_rows, groups, (size_t)n_utt)) != S3A_OK) return rc;
     std::vector<size_t> g_at(cut.size(), 0);
     for (size_t k = 0; k + 1 < cut.size(); k++) g_at[k + 1] = g_at[k] + sb_describe(ud, feat_dev, n_frames, cut[k], cut[k + 1], g_at[k]);
-    HIPCHK(hipMemcpyAsync(ud->sb_gdesc_d, ud->sb_gdesc_h, g_at.back() * sizeof(UwGroup), hipMemcpyHostToDevice, ud->stream));
-    HIPCHK(hipMemcpyAsync(ud->sb_row0_d, ud->sb_row0_h, (size_t)n_utt * 8, hipMemcpyHostToDevice, ud->stream));
+    HIPCHK(hipMemcpyAsync(ud->sb_gdesc.d, ud->sb_gdesc.h, g_at.back() * sizeof(UwGroup), hipMemcpyHostToDevice, ud->stream));
+    HIPCHK(hipMemcpyAsync(ud->sb_row0.d, ud->sb_row0.h, (size_t)n_utt * 8, hipMemcpyHostToDevice, ud->stream));
     /* the order of the takes: within a part the longest utterance first (stable: equal lengths in queue order) -- the launch ends with its
      * slowest lane, and an utterance taken when the counter is nearly through should be a short one */
-    if ((rc = q_grow(&ud->kf_order_d, &ud->kf_order_h, &ud->kf_order_cap, (size_t)n_utt, "queue order")) != S3A_OK) return rc;
+    if ((rc = q_reserve(ud, ud->kf_order, S3A_GROW_DEV | S3A_GROW_PIN, (size_t)n_utt, "queue order")) != S3A_OK) return rc;
     for (size_t k = 0; k + 1 < cut.size(); k++) {
-        for (int32_t u = cut[k]; u < cut[k + 1]; u++) ud->kf_order_h[u] = u;
+        for (int32_t u = cut[k]; u < cut[k + 1]; u++) ud->kf_order.h[u] = u;
         if (!s3a_variants()->kf_queue_in_order)
-            std::stable_sort(ud->kf_order_h + cut[k], ud->kf_order_h + cut[k + 1], [&](int32_t a, int32_t b) { return n_frames[a] > n_frames[b]; });
+            std::stable_sort(ud->kf_order.h + cut[k], ud->kf_order.h + cut[k + 1], [&](int32_t a, int32_t b) { return n_frames[a] > n_frames[b]; });
     }
-    HIPCHK(hipMemcpyAsync(ud->kf_order_d, ud->kf_order_h, (size_t)n_utt * 4, hipMemcpyHostToDevice, ud->stream));
+    HIPCHK(hipMemcpyAsync(ud->kf_order.d, ud->kf_order.h, (size_t)n_utt * 4, hipMemcpyHostToDevice, ud->stream));
     ud->kf_n_score = ud->kf_n_frames = 0;
     for (size_t k = 0; k + 1 < cut.size(); k++) {
         const int32_t u0 = cut[k], nu = cut[k + 1] - cut[k];
@@ -4617,9 +4521,9 @@ kf_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat_dev, c
         HIPCHK(hipMemsetAsync(ud->d_kfnext, 0, 4, ud->stream));
         KfJob J;
         memset(&J, 0, sizeof J);
-        J.mode = KF_QUEUE; J.n_utt = nu; J.u0 = u0; J.order = ud->kf_order_d; J.next = ud->d_kfnext; J.lane_u = ud->d_kfnext + 16; J.stage = ud->q_ctx_d;
-        J.row0 = ud->sb_row0_d; J.scores = ud->sb_scores; J.bests = ud->sb_bests;
-        J.hdr = ud->q_hdr_d; J.words = ud->q_words_d; J.wcount = wcount; J.P = P; J.B = B; J.n_word = ud->cfg.n_word;
+        J.mode = KF_QUEUE; J.n_utt = nu; J.u0 = u0; J.order = ud->kf_order.d; J.next = ud->d_kfnext; J.lane_u = ud->d_kfnext + 16; J.stage = ud->q_ctx.d;
+        J.row0 = ud->sb_row0.d; J.scores = ud->sb_scores.d; J.bests = ud->sb_bests.d;
+        J.hdr = ud->q_hdr.d; J.words = ud->q_words.d; J.wcount = wcount; J.P = P; J.B = B; J.n_word = ud->cfg.n_word;
         if ((rc = kf_launch_chain(ud, min(ud->n_lanes, nu), J)) != S3A_OK) return rc;
         ud->kf_n_frames++;
         kf_mark(ud);
@@ -4683,22 +4587,92 @@ lane_fetch_table(s3a_uttdec_t *ud, int32_t z)
     const int32_t n = hl.h_st[0], nf = hl.nfr + 2;
     hl.n_entry = n;
     const size_t need = (size_t)10 * (n + 1) + (size_t)3 * nf;
-    if (need > hl.h_tab_cap) {
-        const size_t grow = max(need * 2, (size_t)1 << 18);        /* (with slack: see lane_begin) */
-        if (hl.h_tab) (void)hipHostFree(hl.h_tab);
-        hl.h_tab = NULL; hl.h_tab_cap = 0;
-        if (hipHostMalloc((void **)&hl.h_tab, grow * 4 + 64) != hipSuccess) { s3a_set_error("s3a_uttdec: pinned table buffer"); return S3A_ENOMEM; }
-        hl.h_tab_cap = grow;
-    }
+    /* (with slack: see lane_begin) */
+    if (hl.tab.reserve(ud->mem, S3A_GROW_PIN, need, max(need * 2, (size_t)1 << 18), 4, 64) != S3A_OK) { s3a_set_error("s3a_uttdec: pinned table buffer"); return S3A_ENOMEM; }
     const WLane &w = hl.d.w;
     const int32_t *src[10] = { w.score, w.pred, w.lw0, w.lw1, w.wid, w.sf, w.ef, w.ascr, w.lscr, w.type };
     for (int k = 0; k < 10; k++)
-        HIPCHK(hipMemcpyAsync(hl.h_tab + (size_t)k * (n + 1), src[k], (size_t)n * 4, hipMemcpyDeviceToHost, ud->stream));
-    int32_t *tail = hl.h_tab + (size_t)10 * (n + 1);
+        HIPCHK(hipMemcpyAsync(hl.tab.h + (size_t)k * (n + 1), src[k], (size_t)n * 4, hipMemcpyDeviceToHost, ud->stream));
+    int32_t *tail = hl.tab.h + (size_t)10 * (n + 1);
     HIPCHK(hipMemcpyAsync(tail, w.frame_start, (size_t)nf * 4, hipMemcpyDeviceToHost, ud->stream));
     HIPCHK(hipMemcpyAsync(tail + nf, w.bestscore, (size_t)nf * 4, hipMemcpyDeviceToHost, ud->stream));
     HIPCHK(hipMemcpyAsync(tail + 2 * nf, w.bestvh, (size_t)nf * 4, hipMemcpyDeviceToHost, ud->stream));
     return S3A_OK;
+}
+
+/* ---- the steps every decode call is made of (who: the entry point's name, for the error texts) ---- */
+/* what ku_lanes_begin writes as an utterance's history entry 0 (vithist_utt_begin) */
+static UBegin
+utt_begin_par(const s3a_uttdec_t *ud)
+{
+    const s3a_wordlevel_cfg_t &c = ud->cfg;
+    UBegin B;
+    const int32_t e0[10] = { 0 /*score*/, -1 /*pred*/, c.start_lwid, -1 /*lw1*/, c.startwid, -1 /*sf*/, -1 /*ef*/, 0, 0, 0 };
+    memcpy(B.e0, e0, sizeof e0);
+    /* wl_lm_context of entry 0: state (<s>, none): no trigram run, the bigrams of <s> */
+    B.lmc[0] = B.lmc[1] = B.lmc[2] = B.lmc[3] = 0; B.lmc[4] = -1;
+    if (ud->lm->d.n_bg > 0 && c.start_lwid >= 0) { B.lmc[3] = ud->lm->ug_firstbg[c.start_lwid]; B.lmc[4] = ud->lm->ug_firstbg[c.start_lwid + 1] - B.lmc[3]; }
+    B.n_pset = ud->n_pset > 0 ? ud->n_pset : 1;
+    return B;
+}
+
+/* ku_hyp's parameters (wtotal: words the packed buffer holds) */
+static UHypPar
+utt_hyp_par(const s3a_uttdec_t *ud, int32_t wtotal)
+{
+    const s3a_wordlevel_cfg_t &c = ud->cfg;
+    const UHypPar P = { c.finish_lwid, c.finishwid, c.silwid, ud->hyp_wcap, wtotal };
+    return P;
+}
+
+/* -pheurtype: the phoneme look-ahead's tables for whole utterances, behind the ku_lanes_begin of the n lanes lanes[] (NULL: 0 .. n - 1) --
+ * every frame's CI senone scores, every frame's phn_heur_list; max_nfr: their longest utterance */
+static int32_t
+enqueue_pheur_tables(s3a_uttdec_t *ud, int32_t max_nfr, int32_t n, const int32_t *lanes)
+{
+    const UShared &S = ud->S;
+    if (S.pheurtype <= 0) return S3A_OK;
+    const dim3 g((S.n_ci_sen * S.CP + 255) / 256, max_nfr, n);
+    if (ud->exact) hipLaunchKernelGGL(ku_ci_ahead<true>, g, dim3(256), 0, ud->stream, ud->d_lanes, ud->S, lanes);
+    else hipLaunchKernelGGL(ku_ci_ahead<false>, g, dim3(256), 0, ud->stream, ud->d_lanes, ud->S, lanes);
+    hipLaunchKernelGGL(ku_phn_heur, dim3((max_nfr + PH_T - 1) / PH_T, 1, n), dim3(PH_T), 0, ud->stream, ud->d_lanes, ud->S, lanes);
+    HIPCHK(hipGetLastError());
+    return S3A_OK;
+}
+
+/* the close of a call, behind its last copy: wait for the stream, the device time between ev0 and ev1, the marks and the profiled frames'
+ * events; a call that failed (rc) leaves its first n_dirty lanes to be scrubbed.  Returns rc, or what the wait found. */
+static int32_t
+call_close(s3a_uttdec_t *ud, const char *who, int32_t rc, int32_t n_dirty)
+{
+    if (hipStreamSynchronize(ud->stream) != hipSuccess && rc == S3A_OK) { s3a_set_error("%s: %s", who, hipGetErrorString(hipGetLastError())); rc = S3A_EHIP; }
+    if (rc == S3A_OK) {
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, ud->ev0, ud->ev1);
+        ud->last_decode_ms = ms;
+    }
+    kf_collect(ud);
+    for (auto &e : ud->prof_ev) {
+        float ms = 0.0f;
+        if (rc == S3A_OK && hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) { ud->prof_us[e.cls] += 1e3 * ms; ud->prof_n[e.cls]++; }
+        (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b);
+    }
+    ud->prof_ev.clear();
+    if (rc != S3A_OK)
+        for (int32_t z = 0; z < n_dirty; z++) ud->lane[z].dirty = 1;      /* nothing is known about the lanes' state */
+    return rc;
+}
+
+/* an utterance that stopped in mid-frame on the word level's error bits: the message, and the code they map to */
+static int32_t
+report_stopped(const char *who, int32_t utt, int32_t frame, int32_t e)
+{
+    s3a_set_error("%s: utterance %d stopped at frame %d: error bits 0x%x%s%s%s%s%s%s", who, utt, frame, e,
+                  (e & WL_E_OPEN_EXIT) ? " (out.history == -1 at a word exit)" : "",
+                  (e & WL_E_EXITS) ? " (too many word exits)" : "", (e & WL_E_CAND) ? " (candidate buffer full)" : "",
+                  (e & WL_E_TABLE) ? " (history table full)" : "", (e & WL_E_LC) ? " (phone is no left context)" : "",
+                  (e & WL_E_NOLM) ? " (word without LM id)" : "");
+    return (e & (WL_E_EXITS | WL_E_CAND | WL_E_TABLE | WL_E_CALLS)) ? S3A_ENOMEM : S3A_EINVAL;
 }
 
 static int32_t
@@ -4720,28 +4694,11 @@ uttdec_decode(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, const i
         if ((rc = lane_begin(ud, z, feat[z], n_frames[z], feat_stride, feat_on_device)) != S3A_OK) return rc;
         maxT = max(maxT, n_frames[z]);
     }
-    {
-        const s3a_wordlevel_cfg_t &c = ud->cfg;
-        UBegin B;
-        const int32_t e0[10] = { 0 /*score*/, -1 /*pred*/, c.start_lwid, -1 /*lw1*/, c.startwid, -1 /*sf*/, -1 /*ef*/, 0, 0, 0 };
-        memcpy(B.e0, e0, sizeof e0);
-        /* wl_lm_context of entry 0: state (<s>, none): no trigram run, the bigrams of <s> */
-        B.lmc[0] = B.lmc[1] = B.lmc[2] = B.lmc[3] = 0; B.lmc[4] = -1;
-        if (ud->lm->d.n_bg > 0 && c.start_lwid >= 0) { B.lmc[3] = ud->lm->ug_firstbg[c.start_lwid]; B.lmc[4] = ud->lm->ug_firstbg[c.start_lwid + 1] - B.lmc[3]; }
-        B.n_pset = ud->n_pset > 0 ? ud->n_pset : 1;
-        hipLaunchKernelGGL(ku_lanes_end, dim3(8, 2 * ud->S.T, n_utt), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, (const int32_t *)NULL, 0);
-        hipLaunchKernelGGL(ku_lanes_begin, dim3(32, 1, n_utt), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, B, (const int32_t *)NULL, (const int32_t *)NULL, (const UCtx *)NULL);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(ud->S.ctx_all, ud->h_ctx_up, sizeof(UCtx) * n_utt, hipMemcpyHostToDevice, ud->stream));
-        if (ud->S.pheurtype > 0) {
-            /* the phoneme look-ahead's tables for the whole utterance: every frame's CI senone scores, every frame's phn_heur_list */
-            const dim3 g((ud->S.n_ci_sen * ud->S.CP + 255) / 256, maxT, n_utt);
-            if (ud->exact) hipLaunchKernelGGL(ku_ci_ahead<true>, g, dim3(256), 0, ud->stream, ud->d_lanes, ud->S, (const int32_t *)NULL);
-            else hipLaunchKernelGGL(ku_ci_ahead<false>, g, dim3(256), 0, ud->stream, ud->d_lanes, ud->S, (const int32_t *)NULL);
-            hipLaunchKernelGGL(ku_phn_heur, dim3((maxT + PH_T - 1) / PH_T, 1, n_utt), dim3(PH_T), 0, ud->stream, ud->d_lanes, ud->S, (const int32_t *)NULL);
-            HIPCHK(hipGetLastError());
-        }
-    }
+    hipLaunchKernelGGL(ku_lanes_end, dim3(8, 2 * ud->S.T, n_utt), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, (const int32_t *)NULL, 0);
+    hipLaunchKernelGGL(ku_lanes_begin, dim3(32, 1, n_utt), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, utt_begin_par(ud), (const int32_t *)NULL, (const int32_t *)NULL, (const UCtx *)NULL);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ud->S.ctx_all, ud->h_ctx_up, sizeof(UCtx) * n_utt, hipMemcpyHostToDevice, ud->stream));
+    if ((rc = enqueue_pheur_tables(ud, maxT, n_utt, NULL)) != S3A_OK) return rc;
     /* (the engine's two timing events live as long as the engine; the per-launch events of profiled frames are destroyed
      * on every way out) */
     if (!ud->ev0 && (hipEventCreate(&ud->ev0) != hipSuccess || hipEventCreate(&ud->ev1) != hipSuccess)) {
@@ -4778,8 +4735,7 @@ uttdec_decode(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, const i
     /* every lane's hypothesis on the device (before the second pass appends its final entries to the tables); what
      * comes back: the lanes' contexts (error bits, counters), the hypothesis headers, then the words */
     if (rc == S3A_OK) {
-        const s3a_wordlevel_cfg_t &c = ud->cfg;
-        const UHypPar P = { c.finish_lwid, c.finishwid, c.silwid, ud->hyp_wcap, (int32_t)min((long long)ud->n_lanes * ud->hyp_wcap, (long long)INT_MAX) };
+        const UHypPar P = utt_hyp_par(ud, (int32_t)min((long long)ud->n_lanes * ud->hyp_wcap, (long long)INT_MAX));
         if (hipMemsetAsync(ud->d_hyp_hdr + (size_t)n_utt * UH_N, 0, 4, ud->stream) != hipSuccess) rc = S3A_EHIP;
         hipLaunchKernelGGL(ku_hyp, dim3(n_utt), dim3(UH_T), 0, ud->stream, ud->d_lanes, ud->lm->d, ud->dict, P, ud->d_hyp_hdr, ud->d_hyp_words,
                            ud->d_hyp_hdr + (size_t)n_utt * UH_N, (const int32_t *)NULL, (const int32_t *)NULL);
@@ -4790,23 +4746,7 @@ uttdec_decode(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, const i
     if (rc == S3A_OK && (hipMemcpyAsync(ud->h_ctx_dn, ud->S.ctx_all, sizeof(UCtx) * n_utt, hipMemcpyDeviceToHost, ud->stream) != hipSuccess
                          || hipMemcpyAsync(ud->h_hyp_hdr, ud->d_hyp_hdr, ((size_t)n_utt * UH_N + 1) * 4, hipMemcpyDeviceToHost, ud->stream) != hipSuccess
                          || hipMemcpyAsync(ud->h_hyp_words, ud->d_hyp_words, first_words * 24, hipMemcpyDeviceToHost, ud->stream) != hipSuccess)) rc = S3A_EHIP;
-    if (hipStreamSynchronize(ud->stream) != hipSuccess && rc == S3A_OK) { s3a_set_error("s3a_uttdec_decode: %s", hipGetErrorString(hipGetLastError())); rc = S3A_EHIP; }
-    if (rc == S3A_OK) {
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, ud->ev0, ud->ev1);
-        ud->last_decode_ms = ms;
-    }
-    kf_collect(ud);
-    for (auto &e : ud->prof_ev) {
-        float ms = 0.0f;
-        if (rc == S3A_OK && hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) { ud->prof_us[e.cls] += 1e3 * ms; ud->prof_n[e.cls]++; }
-        (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b);
-    }
-    ud->prof_ev.clear();
-    if (rc != S3A_OK) {
-        for (int32_t z = 0; z < n_utt; z++) ud->lane[z].dirty = 1;      /* nothing is known about the lanes' state */
-        return rc;
-    }
+    if ((rc = call_close(ud, "s3a_uttdec_decode", rc, n_utt)) != S3A_OK) return rc;
     tm[3] = now();
     /* the history tables and the per-frame statistics stay on the device until someone asks (s3a_uttdec_result) */
     ud->tables_fetched = 0; ud->fstat_fetched = 0;
@@ -4833,15 +4773,8 @@ uttdec_decode(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, const i
     for (int32_t z = 0; z < n_utt; z++)
         if (ud->lane[z].h_ctx->err) ud->lane[z].dirty = 1;
     for (int32_t z = 0; z < n_utt; z++) {
-        const int32_t e = ud->lane[z].h_ctx->err;
-        if (e) {
-            s3a_set_error("s3a_uttdec_decode: utterance %d stopped at frame %d: error bits 0x%x%s%s%s%s%s%s", z,
-                          ud->lane[z].h_ctx->cf, e, (e & WL_E_OPEN_EXIT) ? " (out.history == -1 at a word exit)" : "",
-                          (e & WL_E_EXITS) ? " (too many word exits)" : "", (e & WL_E_CAND) ? " (candidate buffer full)" : "",
-                          (e & WL_E_TABLE) ? " (history table full)" : "", (e & WL_E_LC) ? " (phone is no left context)" : "",
-                          (e & WL_E_NOLM) ? " (word without LM id)" : "");
-            return (e & (WL_E_EXITS | WL_E_CAND | WL_E_TABLE | WL_E_CALLS)) ? S3A_ENOMEM : S3A_EINVAL;
-        }
+        const UCtx &x = *ud->lane[z].h_ctx;
+        if (x.err) return report_stopped("s3a_uttdec_decode", z, x.cf, x.err);
     }
     return S3A_OK;
 }
@@ -4922,6 +4855,26 @@ q_keep_lattices(s3a_uttdec_t *ud, const int32_t *lanes, const int32_t *utts, int
     return S3A_OK;
 }
 
+/* the end of the queue's utterances utts[] in the lanes lanes[] (n of them; _d: the lists on the device, _h: the same on the host): their
+ * hypotheses into the utterances' slots, the second pass while the tables are still theirs, its result into their slots, the lattices
+ * kept when asked for, then lextree_utt_end.  n_utt: utterances of the queue (where the second pass's word counter is) */
+static int32_t
+enqueue_utts_end(s3a_uttdec_t *ud, int32_t n, const int32_t *lanes_d, const int32_t *utts_d, const int32_t *lanes_h, const int32_t *utts_h,
+                 const UHypPar &P, int32_t n_utt, int32_t *wcount)
+{
+    int32_t rc;
+    hipLaunchKernelGGL(ku_hyp, dim3(n), dim3(UH_T), 0, ud->stream, ud->d_lanes, ud->lm->d, ud->dict, P, ud->q_hdr.d, ud->q_words.d, wcount, lanes_d, utts_d);
+    if (ud->dag) {
+        if ((rc = s3a_dagpass_enqueue_lanes(ud->dag, lanes_d, n, ud->stream)) != S3A_OK) return rc;
+        hipLaunchKernelGGL(ku_dag_store, dim3(n), dim3(UH_T), 0, ud->stream, ud->d_lanes, s3a_dagpass_dev_lanes(ud->dag), s3a_dagpass_hyp_cap(ud->dag),
+                           ud->q_dio.d, ud->q_dw.d, ud->q_dio.d + (size_t)n_utt * DG_IO_N, P.wtotal, lanes_d, utts_d);
+        if (ud->q_keep_lat && (rc = q_keep_lattices(ud, lanes_h, utts_h, n)) != S3A_OK) return rc;
+    }
+    hipLaunchKernelGGL(ku_lanes_end, dim3(8, 2 * ud->S.T, n), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, lanes_d, ud->cfg.n_word);
+    HIPCHK(hipGetLastError());
+    return S3A_OK;
+}
+
 static int32_t
 uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, const int32_t *n_frames, int32_t feat_stride,
                     bool feat_on_device)
@@ -4971,16 +4924,16 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
     /* features: one buffer, rows padded to the scorer's float4 stride, one copy */
     std::vector<const float *> fd((size_t)n_utt);
     if (!feat_on_device) {
-        if ((rc = q_grow(&ud->q_feat_d, &ud->q_feat_h, &ud->q_feat_cap, row0[n_utt] * D4x4, "features")) != S3A_OK) return rc;
+        if ((rc = q_reserve(ud, ud->q_feat, S3A_GROW_DEV | S3A_GROW_PIN, row0[n_utt] * D4x4, "features")) != S3A_OK) return rc;
         for (int32_t u = 0; u < n_utt; u++) {
             for (int32_t t = 0; t < n_frames[u]; t++) {
-                float *row = ud->q_feat_h + (row0[u] + t) * D4x4;
+                float *row = ud->q_feat.h + (row0[u] + t) * D4x4;
                 memcpy(row, feat[u] + (size_t)t * feat_stride, sizeof(float) * ud->veclen);
                 for (int32_t k = ud->veclen; k < D4x4; k++) row[k] = 0.0f;
             }
-            fd[u] = ud->q_feat_d + row0[u] * D4x4;
+            fd[u] = ud->q_feat.d + row0[u] * D4x4;
         }
-        HIPCHK(hipMemcpyAsync(ud->q_feat_d, ud->q_feat_h, row0[n_utt] * D4x4 * 4, hipMemcpyHostToDevice, ud->stream));
+        HIPCHK(hipMemcpyAsync(ud->q_feat.d, ud->q_feat.h, row0[n_utt] * D4x4 * 4, hipMemcpyHostToDevice, ud->stream));
     }
     else {
         if (feat_stride != D4x4) { s3a_set_error("s3a_uttdec_decode_queue_dev: device features must have rows of %d floats (zero padded)", D4x4); return S3A_EINVAL; }
@@ -4998,10 +4951,10 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
     struct Ev { int32_t f, o_el, o_bl, n_end, n_beg, max_nfr; };
     std::vector<Ev> evs;
     std::vector<int32_t> sched, u_lane((size_t)n_utt), u_f0((size_t)n_utt), last_utt((size_t)n, -1);
-    if ((rc = q_grow(&ud->q_ctx_d, &ud->q_ctx_h, &ud->q_ctx_cap, (size_t)n_utt, "contexts")) != S3A_OK) return rc;
+    if ((rc = q_reserve(ud, ud->q_ctx, S3A_GROW_DEV | S3A_GROW_PIN, (size_t)n_utt, "contexts")) != S3A_OK) return rc;
     if (kfq || kfd) {
         for (int32_t u = 0; u < n_utt; u++)
-            if ((rc = utt_context(ud, ud->q_ctx_h[u], fd[u], n_frames[u], 1, 0, u)) != S3A_OK) return rc;
+            if ((rc = utt_context(ud, ud->q_ctx.h[u], fd[u], n_frames[u], 1, 0, u)) != S3A_OK) return rc;
         for (int32_t z = 0; z < n; z++) ud->lane[z].nfr = 0;
         if (kfd) {              /* the groups' lane / utterance lists: [lanes 0 .. m - 1][their utterances] per group */
             for (int32_t k0 = 0; k0 < n_utt; k0 += ud->n_lanes) {
@@ -5019,7 +4972,7 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
         for (int32_t u = 0; u < n_utt; u++) {           /* (queue order = the order of a lane's utterances) */
             const int32_t z = u_lane[u], F = u_f0[u], Fe = ((F + n_frames[u] + E - 1) / E) * E;
             HostLane &hl = ud->lane[z];
-            if ((rc = utt_context(ud, ud->q_ctx_h[u], fd[u], n_frames[u], hl.epoch, F, u)) != S3A_OK) return rc;
+            if ((rc = utt_context(ud, ud->q_ctx.h[u], fd[u], n_frames[u], hl.epoch, F, u)) != S3A_OK) return rc;
             hl.epoch += n_frames[u] + 1;
             hl.nfr = n_frames[u];
             last_utt[z] = u;
@@ -5038,65 +4991,40 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
         }
     }
     const int32_t F_end = evs.empty() ? 0 : evs.back().f;           /* (the last event only ends lanes) */
-    if ((rc = q_grow(&ud->q_sched_d, &ud->q_sched_h, &ud->q_sched_cap, sched.size(), "schedule")) != S3A_OK) return rc;
+    if ((rc = q_reserve(ud, ud->q_sched, S3A_GROW_DEV | S3A_GROW_PIN, sched.size(), "schedule")) != S3A_OK) return rc;
     if (!sched.empty()) {
-        memcpy(ud->q_sched_h, sched.data(), sched.size() * 4);
-        HIPCHK(hipMemcpyAsync(ud->q_sched_d, ud->q_sched_h, sched.size() * 4, hipMemcpyHostToDevice, ud->stream));
+        memcpy(ud->q_sched.h, sched.data(), sched.size() * 4);
+        HIPCHK(hipMemcpyAsync(ud->q_sched.d, ud->q_sched.h, sched.size() * 4, hipMemcpyHostToDevice, ud->stream));
     }
-    HIPCHK(hipMemcpyAsync(ud->q_ctx_d, ud->q_ctx_h, sizeof(UCtx) * n_utt, hipMemcpyHostToDevice, ud->stream));
+    HIPCHK(hipMemcpyAsync(ud->q_ctx.d, ud->q_ctx.h, sizeof(UCtx) * n_utt, hipMemcpyHostToDevice, ud->stream));
     /* results: a header per utterance + the word counter; the words packed (an utterance's hypothesis has at most one word
      * per frame + silence + </s>) */
     const size_t wtotal = min(row0[n_utt] + (size_t)4 * n_utt, (size_t)INT_MAX / 8);
-    if ((rc = q_grow(&ud->q_hdr_d, &ud->q_hdr_h, &ud->q_hdr_cap, (size_t)n_utt * UH_N + 1, "hypothesis headers")) != S3A_OK) return rc;
-    if ((rc = q_grow(&ud->q_words_d, (int32_t **)NULL, &ud->q_words_cap, wtotal * 6, "hypothesis words")) != S3A_OK) return rc;
-    HIPCHK(hipMemsetAsync(ud->q_hdr_d, 0, ((size_t)n_utt * UH_N + 1) * 4, ud->stream));
-    int32_t *wcount = ud->q_hdr_d + (size_t)n_utt * UH_N;
+    if ((rc = q_reserve(ud, ud->q_hdr, S3A_GROW_DEV | S3A_GROW_PIN, (size_t)n_utt * UH_N + 1, "hypothesis headers")) != S3A_OK) return rc;
+    if ((rc = q_reserve(ud, ud->q_words, S3A_GROW_DEV, wtotal * 6, "hypothesis words")) != S3A_OK) return rc;
+    HIPCHK(hipMemsetAsync(ud->q_hdr.d, 0, ((size_t)n_utt * UH_N + 1) * 4, ud->stream));
+    int32_t *wcount = ud->q_hdr.d + (size_t)n_utt * UH_N;
     ud->q_dag = 0;
     if (ud->dag) {
         /* the second pass of the lanes that end at a refill event runs right there, before the lane's table is reused */
-        if ((rc = q_grow(&ud->q_dio_d, &ud->q_dio_h, &ud->q_dio_cap, (size_t)n_utt * DG_IO_N + 1, "second-pass status")) != S3A_OK) return rc;
-        if ((rc = q_grow(&ud->q_dw_d, (int32_t **)NULL, &ud->q_dw_cap, wtotal * 6, "second-pass words")) != S3A_OK) return rc;
-        HIPCHK(hipMemsetAsync(ud->q_dio_d, 0xff, ((size_t)n_utt * DG_IO_N) * 4, ud->stream));
-        HIPCHK(hipMemsetAsync(ud->q_dio_d + (size_t)n_utt * DG_IO_N, 0, 4, ud->stream));
+        if ((rc = q_reserve(ud, ud->q_dio, S3A_GROW_DEV | S3A_GROW_PIN, (size_t)n_utt * DG_IO_N + 1, "second-pass status")) != S3A_OK) return rc;
+        if ((rc = q_reserve(ud, ud->q_dw, S3A_GROW_DEV, wtotal * 6, "second-pass words")) != S3A_OK) return rc;
+        HIPCHK(hipMemsetAsync(ud->q_dio.d, 0xff, ((size_t)n_utt * DG_IO_N) * 4, ud->stream));
+        HIPCHK(hipMemsetAsync(ud->q_dio.d + (size_t)n_utt * DG_IO_N, 0, 4, ud->stream));
         if ((rc = s3a_dagpass_prepare(ud->dag, ud->stream)) != S3A_OK) return rc;
     }
-    const s3a_wordlevel_cfg_t &c = ud->cfg;
-    UBegin B;
-    {
-        const int32_t e0[10] = { 0 /*score*/, -1 /*pred*/, c.start_lwid, -1 /*lw1*/, c.startwid, -1 /*sf*/, -1 /*ef*/, 0, 0, 0 };
-        memcpy(B.e0, e0, sizeof e0);
-        B.lmc[0] = B.lmc[1] = B.lmc[2] = B.lmc[3] = 0; B.lmc[4] = -1;
-        if (ud->lm->d.n_bg > 0 && c.start_lwid >= 0) { B.lmc[3] = ud->lm->ug_firstbg[c.start_lwid]; B.lmc[4] = ud->lm->ug_firstbg[c.start_lwid + 1] - B.lmc[3]; }
-        B.n_pset = ud->n_pset > 0 ? ud->n_pset : 1;
-    }
-    const UHypPar P = { c.finish_lwid, c.finishwid, c.silwid, ud->hyp_wcap, (int32_t)wtotal };
+    const UBegin B = utt_begin_par(ud);
+    const UHypPar P = utt_hyp_par(ud, (int32_t)wtotal);
     /* whatever the engine's last decode left active (it ends its lanes at the NEXT decode's beginning) */
     hipLaunchKernelGGL(ku_lanes_end, dim3(8, 2 * T, n), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, (const int32_t *)NULL, 0);
     HIPCHK(hipGetLastError());
     auto run_event = [&](const Ev &e) -> int32_t {
-        const int32_t *el = ud->q_sched_d + e.o_el, *eu = el + e.n_end, *bl = ud->q_sched_d + e.o_bl, *bu = bl + e.n_beg;
-        if (e.n_end > 0) {
-            hipLaunchKernelGGL(ku_hyp, dim3(e.n_end), dim3(UH_T), 0, ud->stream, ud->d_lanes, ud->lm->d, ud->dict, P, ud->q_hdr_d, ud->q_words_d, wcount, el, eu);
-            if (ud->dag) {
-                const int32_t drc = s3a_dagpass_enqueue_lanes(ud->dag, el, e.n_end, ud->stream);
-                if (drc != S3A_OK) return drc;
-                hipLaunchKernelGGL(ku_dag_store, dim3(e.n_end), dim3(UH_T), 0, ud->stream, ud->d_lanes, s3a_dagpass_dev_lanes(ud->dag), s3a_dagpass_hyp_cap(ud->dag),
-                                   ud->q_dio_d, ud->q_dw_d, ud->q_dio_d + (size_t)n_utt * DG_IO_N, (int32_t)wtotal, el, eu);
-                if (ud->q_keep_lat) {
-                    const int32_t krc = q_keep_lattices(ud, sched.data() + e.o_el, sched.data() + e.o_el + e.n_end, e.n_end);
-                    if (krc != S3A_OK) return krc;
-                }
-            }
-            hipLaunchKernelGGL(ku_lanes_end, dim3(8, 2 * T, e.n_end), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, el, c.n_word);
-        }
+        const int32_t *el = ud->q_sched.d + e.o_el, *eu = el + e.n_end, *bl = ud->q_sched.d + e.o_bl, *bu = bl + e.n_beg;
+        int32_t erc;
+        if (e.n_end > 0 && (erc = enqueue_utts_end(ud, e.n_end, el, eu, sched.data() + e.o_el, sched.data() + e.o_el + e.n_end, P, n_utt, wcount)) != S3A_OK) return erc;
         if (e.n_beg > 0) {
-            hipLaunchKernelGGL(ku_lanes_begin, dim3(32, 1, e.n_beg), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, B, bl, bu, (const UCtx *)ud->q_ctx_d);
-            if (S.pheurtype > 0) {
-                const dim3 g((S.n_ci_sen * S.CP + 255) / 256, e.max_nfr, e.n_beg);
-                if (ud->exact) hipLaunchKernelGGL(ku_ci_ahead<true>, g, dim3(256), 0, ud->stream, ud->d_lanes, ud->S, bl);
-                else hipLaunchKernelGGL(ku_ci_ahead<false>, g, dim3(256), 0, ud->stream, ud->d_lanes, ud->S, bl);
-                hipLaunchKernelGGL(ku_phn_heur, dim3((e.max_nfr + PH_T - 1) / PH_T, 1, e.n_beg), dim3(PH_T), 0, ud->stream, ud->d_lanes, ud->S, bl);
-            }
+            hipLaunchKernelGGL(ku_lanes_begin, dim3(32, 1, e.n_beg), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, B, bl, bu, (const UCtx *)ud->q_ctx.d);
+            if ((erc = enqueue_pheur_tables(ud, e.max_nfr, e.n_beg, bl)) != S3A_OK) return erc;
         }
         HIPCHK(hipGetLastError());
         return S3A_OK;
@@ -5126,38 +5054,17 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
         if (rc == S3A_OK) rc = sb_reserve(ud, max_rows, groups, (size_t)n_utt);
         for (int32_t k0 = 0; k0 < n_utt && rc == S3A_OK; k0 += ud->n_lanes)         /* (rows restart per group: sb_describe; row0 by position in the order) */
             g_at.push_back(g_at.back() + sb_describe(ud, gf.data(), gn.data(), k0, min(n_utt, k0 + ud->n_lanes), g_at.back()));
-        if (rc == S3A_OK && (hipMemcpyAsync(ud->sb_gdesc_d, ud->sb_gdesc_h, g_at.back() * sizeof(UwGroup), hipMemcpyHostToDevice, ud->stream) != hipSuccess
-                             || hipMemcpyAsync(ud->sb_row0_d, ud->sb_row0_h, (size_t)n_utt * 8, hipMemcpyHostToDevice, ud->stream) != hipSuccess)) rc = S3A_EHIP;
+        if (rc == S3A_OK && (hipMemcpyAsync(ud->sb_gdesc.d, ud->sb_gdesc.h, g_at.back() * sizeof(UwGroup), hipMemcpyHostToDevice, ud->stream) != hipSuccess
+                             || hipMemcpyAsync(ud->sb_row0.d, ud->sb_row0.h, (size_t)n_utt * 8, hipMemcpyHostToDevice, ud->stream) != hipSuccess)) rc = S3A_EHIP;
         ud->kf_n_score = ud->kf_n_frames = 0;
         size_t gi = 0;
         for (int32_t k0 = 0; k0 < n_utt && rc == S3A_OK; k0 += ud->n_lanes, gi++) {
             const int32_t m = min(ud->n_lanes, n_utt - k0);
-            const int32_t *bl = ud->q_sched_d + (size_t)2 * k0, *bu = bl + m;
-            hipLaunchKernelGGL(ku_lanes_begin, dim3(32, 1, m), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, B, bl, bu, (const UCtx *)ud->q_ctx_d);
-            if (S.pheurtype > 0) {      /* (the group's longest utterance is its first) */
-                const dim3 g((S.n_ci_sen * S.CP + 255) / 256, gn[k0], m);
-                if (ud->exact) hipLaunchKernelGGL(ku_ci_ahead<true>, g, dim3(256), 0, ud->stream, ud->d_lanes, ud->S, bl);
-                else hipLaunchKernelGGL(ku_ci_ahead<false>, g, dim3(256), 0, ud->stream, ud->d_lanes, ud->S, bl);
-                hipLaunchKernelGGL(ku_phn_heur, dim3((gn[k0] + PH_T - 1) / PH_T, 1, m), dim3(PH_T), 0, ud->stream, ud->d_lanes, ud->S, bl);
-            }
-            kf_mark(ud);
-            if ((rc = sb_score(ud, g_at[gi], g_at[gi + 1] - g_at[gi])) != S3A_OK) break;
-            kf_mark(ud);
-            KfJob J;
-            memset(&J, 0, sizeof J);
-            J.mode = KF_STATIC; J.row0 = ud->sb_row0_d + k0; J.scores = ud->sb_scores; J.bests = ud->sb_bests;
-            if ((rc = kf_launch_chain(ud, m, J)) != S3A_OK) break;
-            ud->kf_n_frames++;
-            kf_mark(ud);
-            hipLaunchKernelGGL(ku_hyp, dim3(m), dim3(UH_T), 0, ud->stream, ud->d_lanes, ud->lm->d, ud->dict, P, ud->q_hdr_d, ud->q_words_d, wcount, bl, bu);
-            if (ud->dag) {
-                if ((rc = s3a_dagpass_enqueue_lanes(ud->dag, bl, m, ud->stream)) != S3A_OK) break;
-                hipLaunchKernelGGL(ku_dag_store, dim3(m), dim3(UH_T), 0, ud->stream, ud->d_lanes, s3a_dagpass_dev_lanes(ud->dag), s3a_dagpass_hyp_cap(ud->dag),
-                                   ud->q_dio_d, ud->q_dw_d, ud->q_dio_d + (size_t)n_utt * DG_IO_N, (int32_t)wtotal, bl, bu);
-                if (ud->q_keep_lat && (rc = q_keep_lattices(ud, sched.data() + (size_t)2 * k0, sched.data() + (size_t)2 * k0 + m, m)) != S3A_OK) break;
-            }
-            hipLaunchKernelGGL(ku_lanes_end, dim3(8, 2 * T, m), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, bl, c.n_word);
-            if (hipGetLastError() != hipSuccess) { s3a_set_error("s3a_uttdec_decode_queue: a launch of the grouped second pass failed"); rc = S3A_EHIP; }
+            const int32_t *bl = ud->q_sched.d + (size_t)2 * k0, *bu = bl + m;
+            hipLaunchKernelGGL(ku_lanes_begin, dim3(32, 1, m), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, B, bl, bu, (const UCtx *)ud->q_ctx.d);
+            if ((rc = enqueue_pheur_tables(ud, gn[k0], m, bl)) != S3A_OK) break;       /* (the group's longest utterance is its first) */
+            if ((rc = kf_static_group(ud, m, ud->sb_row0.d + k0, g_at[gi], g_at[gi + 1] - g_at[gi])) != S3A_OK) break;
+            rc = enqueue_utts_end(ud, m, bl, bu, sched.data() + (size_t)2 * k0, sched.data() + (size_t)2 * k0 + m, P, n_utt, wcount);
         }
     }
     else if (graph_mode) {
@@ -5182,46 +5089,18 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
     while (rc == S3A_OK && ei < evs.size()) rc = run_event(evs[ei++]);
     if (graph_mode && rc == S3A_OK && hipMemsetAsync(ud->d_fgbase, 0, 4, ud->stream) != hipSuccess) rc = S3A_EHIP;
     if (rc == S3A_OK && hipEventRecord(ud->ev1, ud->stream) != hipSuccess) rc = S3A_EHIP;
-    if (rc == S3A_OK && hipMemcpyAsync(ud->q_hdr_h, ud->q_hdr_d, ((size_t)n_utt * UH_N + 1) * 4, hipMemcpyDeviceToHost, ud->stream) != hipSuccess) rc = S3A_EHIP;
-    if (rc == S3A_OK && ud->dag && hipMemcpyAsync(ud->q_dio_h, ud->q_dio_d, ((size_t)n_utt * DG_IO_N + 1) * 4, hipMemcpyDeviceToHost, ud->stream) != hipSuccess) rc = S3A_EHIP;
-    if (hipStreamSynchronize(ud->stream) != hipSuccess && rc == S3A_OK) { s3a_set_error("s3a_uttdec_decode_queue: %s", hipGetErrorString(hipGetLastError())); rc = S3A_EHIP; }
-    if (rc == S3A_OK) {
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, ud->ev0, ud->ev1);
-        ud->last_decode_ms = ms;
-    }
-    kf_collect(ud);
-    for (auto &e : ud->prof_ev) {
-        float ms = 0.0f;
-        if (rc == S3A_OK && hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) { ud->prof_us[e.cls] += 1e3 * ms; ud->prof_n[e.cls]++; }
-        (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b);
-    }
-    ud->prof_ev.clear();
-    if (rc != S3A_OK) {
-        for (int32_t z = 0; z < n; z++) ud->lane[z].dirty = 1;      /* nothing is known about the lanes' state */
-        return rc;
-    }
+    if (rc == S3A_OK && hipMemcpyAsync(ud->q_hdr.h, ud->q_hdr.d, ((size_t)n_utt * UH_N + 1) * 4, hipMemcpyDeviceToHost, ud->stream) != hipSuccess) rc = S3A_EHIP;
+    if (rc == S3A_OK && ud->dag && hipMemcpyAsync(ud->q_dio.h, ud->q_dio.d, ((size_t)n_utt * DG_IO_N + 1) * 4, hipMemcpyDeviceToHost, ud->stream) != hipSuccess) rc = S3A_EHIP;
+    if ((rc = call_close(ud, "s3a_uttdec_decode_queue", rc, n)) != S3A_OK) return rc;
     {
-        const size_t total_words = (size_t)ud->q_hdr_h[(size_t)n_utt * UH_N];
-        if (total_words * 6 > ud->q_words_hcap) {
-            if (ud->q_words_h) (void)hipHostFree(ud->q_words_h);
-            ud->q_words_h = NULL; ud->q_words_hcap = 0;
-            const size_t grow = total_words * 6 + total_words + 1024;
-            if (hipHostMalloc((void **)&ud->q_words_h, grow * 4) != hipSuccess) { s3a_set_error("s3a_uttdec_decode_queue: pinned word buffer"); return S3A_ENOMEM; }
-            ud->q_words_hcap = grow;
-        }
-        if (total_words > 0) HIPCHK(hipMemcpy(ud->q_words_h, ud->q_words_d, total_words * 24, hipMemcpyDeviceToHost));
+        const size_t total_words = (size_t)ud->q_hdr.h[(size_t)n_utt * UH_N];
+        if (ud->q_words_pin.reserve(ud->mem, S3A_GROW_PIN, total_words * 6, total_words * 6 + total_words + 1024) != S3A_OK) { s3a_set_error("s3a_uttdec_decode_queue: pinned word buffer"); return S3A_ENOMEM; }
+        if (total_words > 0) HIPCHK(hipMemcpy(ud->q_words_pin.h, ud->q_words.d, total_words * 24, hipMemcpyDeviceToHost));
     }
     if (ud->dag) {
-        const size_t total_words = (size_t)ud->q_dio_h[(size_t)n_utt * DG_IO_N];
-        if (total_words * 6 > ud->q_dw_hcap) {
-            if (ud->q_dw_h) (void)hipHostFree(ud->q_dw_h);
-            ud->q_dw_h = NULL; ud->q_dw_hcap = 0;
-            const size_t grow = total_words * 6 + total_words + 1024;
-            if (hipHostMalloc((void **)&ud->q_dw_h, grow * 4) != hipSuccess) { s3a_set_error("s3a_uttdec_decode_queue: pinned word buffer (second pass)"); return S3A_ENOMEM; }
-            ud->q_dw_hcap = grow;
-        }
-        if (total_words > 0) HIPCHK(hipMemcpy(ud->q_dw_h, ud->q_dw_d, min(total_words, wtotal) * 24, hipMemcpyDeviceToHost));
+        const size_t total_words = (size_t)ud->q_dio.h[(size_t)n_utt * DG_IO_N];
+        if (ud->q_dw_pin.reserve(ud->mem, S3A_GROW_PIN, total_words * 6, total_words * 6 + total_words + 1024) != S3A_OK) { s3a_set_error("s3a_uttdec_decode_queue: pinned word buffer (second pass)"); return S3A_ENOMEM; }
+        if (total_words > 0) HIPCHK(hipMemcpy(ud->q_dw_pin.h, ud->q_dw.d, min(total_words, wtotal) * 24, hipMemcpyDeviceToHost));
         ud->q_dag = 1;
     }
     ud->q_n = n_utt;
@@ -5229,18 +5108,10 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
     /* a lane whose LAST utterance stopped in mid-frame starts the next decode from scratch (the others of its utterances
      * that stopped were scrubbed on the device when the lane took its next one) */
     for (int32_t z = 0; z < n; z++)
-        if (last_utt[z] >= 0 && ud->q_hdr_h[(size_t)last_utt[z] * UH_N + UH_ERR]) ud->lane[z].dirty = 1;
+        if (last_utt[z] >= 0 && ud->q_hdr.h[(size_t)last_utt[z] * UH_N + UH_ERR]) ud->lane[z].dirty = 1;
     for (int32_t u = 0; u < n_utt; u++) {
-        const int32_t *h = ud->q_hdr_h + (size_t)u * UH_N;
-        const int32_t e = h[UH_ERR];
-        if (e) {
-            s3a_set_error("s3a_uttdec_decode_queue: utterance %d stopped at frame %d: error bits 0x%x%s%s%s%s%s%s", u, h[UH_CF], e,
-                          (e & WL_E_OPEN_EXIT) ? " (out.history == -1 at a word exit)" : "",
-                          (e & WL_E_EXITS) ? " (too many word exits)" : "", (e & WL_E_CAND) ? " (candidate buffer full)" : "",
-                          (e & WL_E_TABLE) ? " (history table full)" : "", (e & WL_E_LC) ? " (phone is no left context)" : "",
-                          (e & WL_E_NOLM) ? " (word without LM id)" : "");
-            return (e & (WL_E_EXITS | WL_E_CAND | WL_E_TABLE | WL_E_CALLS)) ? S3A_ENOMEM : S3A_EINVAL;
-        }
+        const int32_t *h = ud->q_hdr.h + (size_t)u * UH_N;
+        if (h[UH_ERR]) return report_stopped("s3a_uttdec_decode_queue", u, h[UH_CF], h[UH_ERR]);
     }
     return S3A_OK;
 }
@@ -5288,7 +5159,7 @@ s3a_uttdec_result(s3a_uttdec_t *ud, int32_t lane, s3a_utt_result_t *out)
     if ((rc = uttdec_fetch(ud, true)) != S3A_OK) return rc;
     const HostLane &hl = ud->lane[lane];
     const int32_t n = hl.n_entry, nf = hl.nfr + 2;
-    const int32_t *t = hl.h_tab;
+    const int32_t *t = hl.tab.h;
     memset(out, 0, sizeof *out);
     out->err = hl.h_ctx->err; out->n_entry = n; out->n_frm = hl.h_st[1]; out->n_frames = hl.nfr;
     out->score = t; out->pred = t + (size_t)(n + 1); out->lw0 = t + (size_t)2 * (n + 1); out->lw1 = t + (size_t)3 * (n + 1);
@@ -5384,11 +5255,10 @@ s3a_uttdec_enable_pheur(s3a_uttdec_t *ud, int32_t pheurtype, int32_t pl_beam, in
         for (int32_t j = 0; j < S.n_ci_sen; j++)         /* (entry n_ci_sen is only compared with) */
             if (sen2cimap[j] < 0 || sen2cimap[j] >= n_ci) { s3a_set_error("s3a_uttdec_enable_pheur: sen2cimap[%d] = %d", j, sen2cimap[j]); return S3A_EINVAL; }
         uint8_t *d_ci = NULL; int16_t *d_s2c = NULL;
-        if (hipMalloc((void **)&d_ci, (size_t)S.N) != hipSuccess || hipMalloc((void **)&d_s2c, (size_t)(S.n_ci_sen + 1) * 2) != hipSuccess
+        if (!ud->mem.dev(d_ci, (size_t)S.N) || !ud->mem.dev(d_s2c, (size_t)(S.n_ci_sen + 1) * 2)
             || hipMemcpy(d_ci, h.data(), (size_t)S.N, hipMemcpyHostToDevice) != hipSuccess
             || hipMemcpy(d_s2c, sen2cimap, (size_t)(S.n_ci_sen + 1) * 2, hipMemcpyHostToDevice) != hipSuccess) {
-            if (d_ci) (void)hipFree(d_ci);
-            if (d_s2c) (void)hipFree(d_s2c);
+            ud->mem.release(d_ci); ud->mem.release(d_s2c);
             s3a_set_error("s3a_uttdec_enable_pheur: device allocation failed");
             return S3A_ENOMEM;
         }
@@ -5396,10 +5266,9 @@ s3a_uttdec_enable_pheur(s3a_uttdec_t *ud, int32_t pheurtype, int32_t pl_beam, in
         std::vector<ULane> tmp((size_t)ud->n_lanes);
         for (int32_t z = 0; z < ud->n_lanes; z++) {
             ULane &u = ud->lane[z].d;
-            if (hipMalloc((void **)&u.ci_all, (size_t)ud->max_frames * S.n_ci_sen * 4) != hipSuccess
-                || hipMalloc((void **)&u.heur_all, (size_t)ud->max_frames * n_ci * 4) != hipSuccess
-                || hipMalloc((void **)&u.hth_pos, (size_t)3 * S.N * 4) != hipSuccess      /* (+ ku_weak_heur's survivors) */
-                || hipMalloc((void **)&u.ph_scratch, ((size_t)3 * S.n_ci_sen + 8) * 4) != hipSuccess) {
+            if (!ud->mem.dev(u.ci_all, (size_t)ud->max_frames * S.n_ci_sen * 4) || !ud->mem.dev(u.heur_all, (size_t)ud->max_frames * n_ci * 4)
+                || !ud->mem.dev(u.hth_pos, (size_t)3 * S.N * 4)      /* (+ ku_weak_heur's survivors) */
+                || !ud->mem.dev(u.ph_scratch, ((size_t)3 * S.n_ci_sen + 8) * 4)) {
                 s3a_set_error("s3a_uttdec_enable_pheur: device allocation failed");
                 return S3A_ENOMEM;
             }
@@ -5445,7 +5314,7 @@ s3a_uttdec_queue_bestpath_hyp(s3a_uttdec_t *ud, int32_t utt, const char *uttid, 
 {
     if (!ud || !hdr || utt < 0 || utt >= ud->q_n || max_words < 0 || (max_words > 0 && !words)) return S3A_EINVAL;
     if (!ud->q_dag) { s3a_set_error("s3a_uttdec_queue_bestpath_hyp: the last queue ran without the second pass (s3a_uttdec_enable_bestpath)"); return S3A_EINVAL; }
-    const int32_t *h = ud->q_hdr_h + (size_t)utt * UH_N, *io = ud->q_dio_h + (size_t)utt * DG_IO_N;
+    const int32_t *h = ud->q_hdr.h + (size_t)utt * UH_N, *io = ud->q_dio.h + (size_t)utt * DG_IO_N;
     memset(hdr, 0, sizeof *hdr);
     if (uttid) strncpy(hdr->uttid, uttid, sizeof hdr->uttid - 1);
     hdr->utt_index = utt_index; hdr->n_frames = ud->q_nfr[utt]; hdr->n_entry = io[DG_IO_NENT]; hdr->exit_id = io[DG_IO_ENDID];
@@ -5464,7 +5333,7 @@ s3a_uttdec_queue_bestpath_hyp(s3a_uttdec_t *ud, int32_t utt, const char *uttid, 
     hdr->n_words = io[DG_IO_NWORDS];
     if (io[UD_WOFF] < 0) { s3a_set_error("s3a_uttdec_queue_bestpath_hyp: the packed word buffer was too small"); return S3A_ENOMEM; }
     if (hdr->n_words > max_words) { hdr->status = -3; return S3A_OK; }
-    const int32_t *w = ud->q_dw_h + (size_t)io[UD_WOFF] * 6;
+    const int32_t *w = ud->q_dw_pin.h + (size_t)io[UD_WOFF] * 6;
     for (int32_t q = 0; q < hdr->n_words; q++) {
         s3a_hyp_word_t &o = words[q];
         o.wid = w[6 * q]; o.sf = w[6 * q + 1]; o.ef = w[6 * q + 2]; o.ascr = w[6 * q + 3]; o.lscr = w[6 * q + 4]; o.scale = w[6 * q + 5];
@@ -5598,14 +5467,14 @@ s3a_uttdec_window(const s3a_uttdec_t *ud)
 /* the word level on its own (parity tests: frame by frame against the oracle) */
 /* ------------------------------------------------------------------ */
 struct s3a_wltest_s {
+    s3a_hostmem mem;
     s3a_lm3g_t *lm;
     WDict dict;
     WPar par;
     ULane lane, *d_lane;
     UCtx *h_ctx;
-    int32_t *d_lcmap, *h_pack, *h_tab;
+    int32_t *d_lcmap, *h_pack;
     int32_t T, n_ci, n_word, start_lwid, max_exits, cap, max_frames;
-    size_t h_tab_cap;
     hipStream_t stream;
 };
 
@@ -5613,13 +5482,7 @@ extern "C" void
 s3a_wltest_free(s3a_wltest_t *wt)
 {
     if (!wt) return;
-    wlane_free(wt->lane.w);
-    const void *q[] = { wt->dict.lwid, wt->dict.fillpen, wt->dict.last_ci, wt->dict.is_filler, wt->d_lcmap, wt->lane.ctx,
-                        wt->lane.pack, wt->d_lane };
-    for (auto p : q) if (p) (void)hipFree((void *)p);
-    if (wt->h_ctx) (void)hipHostFree(wt->h_ctx);
-    if (wt->h_pack) (void)hipHostFree(wt->h_pack);
-    if (wt->h_tab) (void)hipHostFree(wt->h_tab);
+    wt->mem.free_all();
     if (wt->stream) (void)hipStreamDestroy(wt->stream);
     delete wt;
 }
@@ -5634,8 +5497,7 @@ s3a_wltest_init(s3a_lm3g_t *lm, const s3a_wordlevel_cfg_t *cfg, const int32_t *l
         s3a_set_error("s3a_wltest_init: bad arguments");
         return NULL;
     }
-    s3a_wltest_t *wt = new s3a_wltest_s();
-    memset((void *)wt, 0, sizeof *wt);
+    s3a_wltest_t *wt = new s3a_wltest_s();      /* (value-initialised) */
     wt->lm = lm; wt->T = 2 * cfg->n_lextree; wt->n_ci = cfg->n_ci; wt->n_word = cfg->n_word; wt->start_lwid = cfg->start_lwid;
     wt->max_exits = max_exits; wt->cap = vh_cap; wt->max_frames = max_frames;
     const int32_t T = wt->T, hdr = 6 * T + 16;
@@ -5647,25 +5509,24 @@ s3a_wltest_init(s3a_lm3g_t *lm, const s3a_wordlevel_cfg_t *cfg, const int32_t *l
     int32_t *p0 = NULL, *p1 = NULL, *p2 = NULL;
     uint8_t *p3 = NULL;
     if (hipStreamCreateWithFlags(&wt->stream, hipStreamNonBlocking) != hipSuccess) { s3a_set_error("s3a_wltest_init: no HIP device"); delete wt; return NULL; }
-    DM(p0, (size_t)cfg->n_word * 4); DM(p1, (size_t)cfg->n_word * 4); DM(p2, (size_t)cfg->n_word * 4); DM(p3, (size_t)cfg->n_word);
+    DM(wt->mem, p0, (size_t)cfg->n_word * 4); DM(wt->mem, p1, (size_t)cfg->n_word * 4); DM(wt->mem, p2, (size_t)cfg->n_word * 4); DM(wt->mem, p3, (size_t)cfg->n_word);
     wt->dict.lwid = p0; wt->dict.fillpen = p1; wt->dict.last_ci = p2; wt->dict.is_filler = p3;
     wt->dict.n_word = cfg->n_word; wt->dict.n_ci = cfg->n_ci;
     if (hipMemcpy(p0, cfg->lwid, (size_t)cfg->n_word * 4, hipMemcpyHostToDevice) != hipSuccess
         || hipMemcpy(p1, cfg->fillpen, (size_t)cfg->n_word * 4, hipMemcpyHostToDevice) != hipSuccess
         || hipMemcpy(p2, cfg->last_ci, (size_t)cfg->n_word * 4, hipMemcpyHostToDevice) != hipSuccess
         || hipMemcpy(p3, cfg->is_filler, (size_t)cfg->n_word, hipMemcpyHostToDevice) != hipSuccess) goto fail;
-    UPV(wt->d_lcmap, lcmap);
+    UPV(wt->mem, wt->d_lcmap, lcmap);
     wt->par.wbeam = cfg->wbeam_vh; wt->par.bghist = cfg->bghist; wt->par.maxwpf = cfg->maxwpf; wt->par.maxhist = cfg->maxhistpf;
     wt->par.wordend = cfg->wordend_beam; wt->par.n_lextree = cfg->n_lextree; wt->par.epl = cfg->epl; wt->par.T = T;
     wt->par.hmmbeam = cfg->hmmbeam; wt->par.lcmap = wt->d_lcmap;
     for (int32_t t = 0; t < T; t++) wt->par.tree_type[t] = cfg->tree_type[t];
-    if (wlane_alloc(wt->lane.w, vh_cap, max_frames, max_exits, cand_cap, cand_cap < (1 << 18) ? cand_cap : (1 << 18), cfg->n_word, wt->stream) != S3A_OK) goto fail;
-    DM(wt->lane.ctx, sizeof(UCtx));
-    DM(wt->lane.pack, (size_t)(hdr + 3 * max_exits) * 4);
-    DM(wt->d_lane, sizeof(ULane));
+    if (wlane_alloc(wt->mem, wt->lane.w, vh_cap, max_frames, max_exits, cand_cap, cand_cap < (1 << 18) ? cand_cap : (1 << 18), cfg->n_word, wt->stream) != S3A_OK) goto fail;
+    DM(wt->mem, wt->lane.ctx, sizeof(UCtx));
+    DM(wt->mem, wt->lane.pack, (size_t)(hdr + 3 * max_exits) * 4);
+    DM(wt->mem, wt->d_lane, sizeof(ULane));
     if (hipMemcpy(wt->d_lane, &wt->lane, sizeof(ULane), hipMemcpyHostToDevice) != hipSuccess
-        || hipHostMalloc((void **)&wt->h_ctx, sizeof(UCtx)) != hipSuccess
-        || hipHostMalloc((void **)&wt->h_pack, (size_t)(hdr + 3 * max_exits) * 4) != hipSuccess) goto fail;
+        || !wt->mem.pin(wt->h_ctx, sizeof(UCtx)) || !wt->mem.pin(wt->h_pack, (size_t)(hdr + 3 * max_exits) * 4)) goto fail;
     return wt;
 fail:
     s3a_wltest_free(wt);
@@ -5789,7 +5650,7 @@ s3a_uttdec_queue_hyp(s3a_uttdec_t *ud, int32_t utt, const char *uttid, int32_t u
                      s3a_hyp_word_t *words, int32_t max_words)
 {
     if (!ud || !hdr || utt < 0 || utt >= ud->q_n || max_words < 0 || (max_words > 0 && !words)) return S3A_EINVAL;
-    return hyp_from_header(ud->q_hdr_h + (size_t)utt * UH_N, ud->q_words_h, ud->q_nfr[utt], utt, uttid, utt_index, hdr, words, max_words);
+    return hyp_from_header(ud->q_hdr.h + (size_t)utt * UH_N, ud->q_words_pin.h, ud->q_nfr[utt], utt, uttid, utt_index, hdr, words, max_words);
 }
 
 /* ... and what stopped it, if anything: the word level's error bits (0: decoded), the frame it stopped at, the largest
@@ -5798,7 +5659,7 @@ extern "C" int32_t
 s3a_uttdec_queue_status(s3a_uttdec_t *ud, int32_t utt, int32_t *err, int32_t *stopped_at, int32_t *max_cand, int32_t *max_new)
 {
     if (!ud || utt < 0 || utt >= ud->q_n) return S3A_EINVAL;
-    const int32_t *h = ud->q_hdr_h + (size_t)utt * UH_N;
+    const int32_t *h = ud->q_hdr.h + (size_t)utt * UH_N;
     if (err) *err = h[UH_ERR];
     if (stopped_at) *stopped_at = h[UH_CF];
     if (max_cand) *max_cand = h[UH_MAXCAND];
