@@ -587,7 +587,8 @@ struct s3a_batch_s {
     BOut out[BMAXSLOT];
     uint8_t has_trans[BMAXSLOT], active[BMAXSLOT], arrived[BMAXSLOT];
     int32_t n_active, n_arrived, order[BMAXSLOT], rows[BMAXSLOT], zof[BMAXSLOT], last_order[BMAXSLOT], last_n;
-    int32_t *h_pack, pack_stride, pack_max_exits, hdr_max;     /* pinned host: the kernels write the frame records there */
+    s3a_grow<int32_t> pack;             /* pinned host (.h): the kernels write the frame records there */
+    int32_t pack_stride, pack_max_exits, hdr_max;
     int32_t g_ent, g_ci, g_cd, g_maxn, g_N, g_T, g_mark, g_tmat, exact;
     unsigned long long gen;
     long steps, slot_frames;
@@ -595,25 +596,24 @@ struct s3a_batch_s {
     hipEvent_t ev;
     pthread_mutex_t mu;
     pthread_cond_t cv;
+    s3a_hostmem mem;                    /* every device / pinned buffer above is its */
 };
 
 extern "C" s3a_batch_t *
 s3a_batch_create(int32_t max_slots)
 {
     if (max_slots <= 0 || max_slots > BMAXSLOT) { s3a_set_error("s3a_batch_create: 1..%d slots", BMAXSLOT); return NULL; }
-    s3a_batch_t *b = new s3a_batch_s();
-    memset((void *)b, 0, sizeof *b);
+    s3a_batch_t *b = new s3a_batch_s();        /* (value-initialised) */
     b->max_slots = max_slots;
     b->opt_scan_chained = s3a_variants()->scan_chained != 0;
     pthread_mutex_init(&b->mu, NULL);
     pthread_cond_init(&b->cv, NULL);
     if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess
         || hipEventCreateWithFlags(&b->ev, hipEventDisableTiming) != hipSuccess
-        || hipMalloc((void **)&b->d_slots, sizeof(BSlot) * max_slots) != hipSuccess
-        || hipMalloc((void **)&b->d_frames, sizeof(BFrame) * max_slots) != hipSuccess
-        || hipHostMalloc((void **)&b->h_frames, sizeof(BFrame) * max_slots) != hipSuccess) {
+        || !b->mem.dev(b->d_slots, sizeof(BSlot) * max_slots) || !b->mem.dev(b->d_frames, sizeof(BFrame) * max_slots)
+        || !b->mem.pin(b->h_frames, sizeof(BFrame) * max_slots)) {
         s3a_set_error("s3a_batch_create: no usable HIP device (libcmusphinx_amd has no CPU fallback)");
-        delete b;
+        s3a_batch_free(b);
         return NULL;
     }
     return b;
@@ -623,10 +623,9 @@ extern "C" void
 s3a_batch_free(s3a_batch_t *b)
 {
     if (!b) return;
-    (void)hipStreamSynchronize(b->stream);
-    (void)hipEventDestroy(b->ev);
-    (void)hipFree(b->d_slots); (void)hipFree(b->d_frames); (void)hipHostFree(b->h_frames);
-    if (b->h_pack) (void)hipHostFree(b->h_pack);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    if (b->ev) (void)hipEventDestroy(b->ev);
+    b->mem.free_all();
 
     /* the attached decoders now own a dead stream handle: they must be freed by their owners
      * WITHOUT further use; their own streams were replaced at attach time */
@@ -696,13 +695,11 @@ s3a_batch_attach(s3a_batch_t *b, s3a_lexsearch_t *ls, s3a_scorer_t *sc, s3a_coms
         b->g_mark = max(b->g_mark, (ls->ent_cap + DBLOCK - 1) / DBLOCK + ((maxn + DBLOCK - 1) / DBLOCK) * s.T);
         b->g_tmat = max(b->g_tmat, s.n_tmat);
         const int32_t hdr = 6 * s.T + 16;
-        if (hdr > b->hdr_max || ls->pack_max_exits > b->pack_max_exits) {
-            if (b->h_pack) (void)hipHostFree(b->h_pack);
-            b->hdr_max = max(b->hdr_max, hdr);
-            b->pack_max_exits = max(b->pack_max_exits, ls->pack_max_exits);
-            b->pack_stride = b->hdr_max + 3 * b->pack_max_exits;
-            if (hipHostMalloc((void **)&b->h_pack, (size_t)b->pack_stride * b->max_slots * 4, hipHostMallocCoherent) != hipSuccess) { rc = S3A_EHIP; break; }
-        }
+        b->hdr_max = max(b->hdr_max, hdr);
+        b->pack_max_exits = max(b->pack_max_exits, ls->pack_max_exits);
+        b->pack_stride = b->hdr_max + 3 * b->pack_max_exits;   /* (grows when either did) */
+        const size_t pack_words = (size_t)b->pack_stride * b->max_slots;
+        if (b->pack.reserve(b->mem, S3A_GROW_PIN, pack_words, pack_words, 4, 0, hipHostMallocCoherent) != S3A_OK) { rc = S3A_EHIP; break; }
         b->n_slots++;
     } while (0);
     pthread_mutex_unlock(&b->mu);
@@ -819,7 +816,7 @@ run_batch(s3a_batch_t *b)
         hipLaunchKernelGGL(kb_resolve, dim3((b->g_N + RSBLOCK - 1) / RSBLOCK, 1, n), dim3(RSBLOCK), 0, st, S, F);
         {
             const int32_t scan_nc = scan_workgroups(g_rows, b->opt_scan_chained);
-            hipLaunchKernelGGL(kb_scan, dim3(b->g_T * scan_nc, 1, n), dim3(SCAN_THREADS), 0, st, S, F, b->h_pack,
+            hipLaunchKernelGGL(kb_scan, dim3(b->g_T * scan_nc, 1, n), dim3(SCAN_THREADS), 0, st, S, F, b->pack.h,
                                b->pack_stride, b->pack_max_exits, scan_nc);
         }
         CHK(hipGetLastError());
@@ -855,7 +852,7 @@ unpack_own(s3a_batch_t *b, int32_t slot)
     if (o.rc != S3A_OK) { s3a_set_error("%s", o.err); return o.rc; }
     s3a_lexsearch_t *ls = b->ls[slot];
     const int32_t z = b->zof[slot], hdr = 6 * ls->n_tree + 16;
-    const int32_t *p = b->h_pack + (size_t)z * b->pack_stride;
+    const int32_t *p = b->pack.h + (size_t)z * b->pack_stride;
     int32_t total = 0;
     int32_t rc = s3a_dec_unpack(ls, p, o.may_hist != 0, o.frm, o.res, o.n_exit, o.max_exits, &total);
     if (rc != S3A_OK) return rc;

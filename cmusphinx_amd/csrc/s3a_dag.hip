@@ -604,13 +604,14 @@ struct s3a_dagpass_s {
     DagShared G;
     int32_t n_lanes, max_frames, device;
     std::vector<DagLane> lane;
-    std::vector<int32_t *> arena, own_tab;      /* device allocations per lane */
+    std::vector<int32_t *> own_tab;              /* per lane: s3a_dagpass_run_tables' device tables */
     DagLane *d_lanes;
     int32_t *d_cfg;                              /* basewid | lwid | fillpen */
     uint8_t *d_fill;
     int32_t *h_io, *h_out;                       /* pinned: [n_lanes][DG_IO_N], [n_lanes][5 * hyp_cap] */
     int32_t n_run;
     bool lanes_dirty;
+    s3a_hostmem mem;                             /* every device / pinned buffer above is its */
 };
 
 extern "C" void
@@ -619,13 +620,7 @@ s3a_dagpass_free(s3a_dagpass_t *dp)
     if (!dp) return;
     (void)hipSetDevice(dp->device);
     (void)hipDeviceSynchronize();
-    for (auto p : dp->arena) if (p) (void)hipFree(p);
-    for (auto p : dp->own_tab) if (p) (void)hipFree(p);
-    if (dp->d_lanes) (void)hipFree(dp->d_lanes);
-    if (dp->d_cfg) (void)hipFree(dp->d_cfg);
-    if (dp->d_fill) (void)hipFree(dp->d_fill);
-    if (dp->h_io) (void)hipHostFree(dp->h_io);
-    if (dp->h_out) (void)hipHostFree(dp->h_out);
+    dp->mem.free_all();
     delete dp;
 }
 
@@ -639,9 +634,9 @@ s3a_dagpass_init(s3a_lm3g_t *lm, const s3a_dag_cfg_t *cfg, int32_t n_lanes, int3
         return NULL;
     }
     if (!lm->d.ug_prob) { s3a_set_error("s3a_dagpass_init: the LM handle has no device arrays (s3a_lm3g_init_host)"); return NULL; }
-    s3a_dagpass_t *dp = new s3a_dagpass_s();
-    dp->lm = lm; dp->n_lanes = n_lanes; dp->max_frames = max_frames; dp->d_lanes = NULL; dp->d_cfg = NULL; dp->d_fill = NULL;
-    dp->h_io = dp->h_out = NULL; dp->n_run = 0; dp->lanes_dirty = true; dp->device = 0;
+    s3a_dagpass_t *dp = new s3a_dagpass_s();   /* (value-initialised) */
+    s3a_hostmem &m = dp->mem;
+    dp->lm = lm; dp->n_lanes = n_lanes; dp->max_frames = max_frames; dp->lanes_dirty = true;
     (void)hipGetDevice(&dp->device);
     DagShared &G = dp->G;
     memset(&G, 0, sizeof G);
@@ -660,7 +655,7 @@ s3a_dagpass_init(s3a_lm3g_t *lm, const s3a_dag_cfg_t *cfg, int32_t n_lanes, int3
     G.finish_lwid = cfg->finish_lwid; G.wip = cfg->wip; G.lwf = cfg->lwf;
     {
         const size_t nw = (size_t)cfg->n_word;
-        if (hipMalloc((void **)&dp->d_cfg, nw * 12) != hipSuccess || hipMalloc((void **)&dp->d_fill, nw) != hipSuccess
+        if (!m.dev(dp->d_cfg, nw * 12) || !m.dev(dp->d_fill, nw)
             || hipMemcpy(dp->d_cfg, cfg->basewid, nw * 4, hipMemcpyHostToDevice) != hipSuccess
             || hipMemcpy(dp->d_cfg + nw, cfg->lwid, nw * 4, hipMemcpyHostToDevice) != hipSuccess
             || hipMemcpy(dp->d_cfg + 2 * nw, cfg->fillpen, nw * 4, hipMemcpyHostToDevice) != hipSuccess
@@ -672,19 +667,18 @@ s3a_dagpass_init(s3a_lm3g_t *lm, const s3a_dag_cfg_t *cfg, int32_t n_lanes, int3
         G.basewid = dp->d_cfg; G.lwid = dp->d_cfg + nw; G.fillpen = dp->d_cfg + 2 * nw; G.is_filler = dp->d_fill;
     }
     dp->lane.resize(n_lanes);
-    dp->arena.assign(n_lanes, NULL); dp->own_tab.assign(n_lanes, NULL);
+    dp->own_tab.assign(n_lanes, NULL);
     /* one arena of 32-bit words per lane, carved (64-bit arrays first: alignment) */
     const size_t H1 = (size_t)G.h1mask + 1, BH = (size_t)G.bmask + 1, Fw = (size_t)G.F + 2, Nw = (size_t)E + 2;
     const size_t words = 2 * (3 * H1 + 2 * BH) + 3 * H1 + 9 * (size_t)E + 10 * Fw + 15 * Nw + 3 * (size_t)G.link_cap + 7 * BH
         + 2 * (size_t)G.task_cap + DG_IO_N + 2 * (size_t)G.hyp_cap + 5 * (size_t)G.hyp_cap + 64;
     for (int32_t z = 0; z < n_lanes; z++) {
         int32_t *a = NULL;
-        if (hipMalloc((void **)&a, words * 4) != hipSuccess) {
+        if (!m.dev(a, words * 4)) {
             s3a_set_error("s3a_dagpass_init: out of device memory (%zu MB per lane)", words * 4 >> 20);
             s3a_dagpass_free(dp);
             return NULL;
         }
-        dp->arena[z] = a;
         DagLane &L = dp->lane[z];
         memset((void *)&L, 0, sizeof L);
         unsigned long long *q = (unsigned long long *)a;
@@ -704,9 +698,8 @@ s3a_dagpass_init(s3a_lm3g_t *lm, const s3a_dag_cfg_t *cfg, int32_t n_lanes, int3
 #undef CARVE
         if (hipMemset(L.io, 0, DG_IO_N * 4) != hipSuccess) { s3a_dagpass_free(dp); return NULL; }
     }
-    if (hipMalloc((void **)&dp->d_lanes, sizeof(DagLane) * n_lanes) != hipSuccess
-        || hipHostMalloc((void **)&dp->h_io, (size_t)n_lanes * DG_IO_N * 4) != hipSuccess
-        || hipHostMalloc((void **)&dp->h_out, (size_t)n_lanes * 5 * G.hyp_cap * 4) != hipSuccess) {
+    if (!m.dev(dp->d_lanes, sizeof(DagLane) * n_lanes) || !m.pin(dp->h_io, (size_t)n_lanes * DG_IO_N * 4)
+        || !m.pin(dp->h_out, (size_t)n_lanes * 5 * G.hyp_cap * 4)) {
         s3a_set_error("s3a_dagpass_init: allocation failed");
         s3a_dagpass_free(dp);
         return NULL;
@@ -925,7 +918,7 @@ s3a_dagpass_run_tables(s3a_dagpass_t *dp, int32_t n_utt, const s3a_dag_table_t *
             return S3A_EINVAL;
         }
         if (!dp->own_tab[z]) {
-            if (hipMalloc((void **)&dp->own_tab[z], ((size_t)10 * E + F + 16) * 4) != hipSuccess) { s3a_set_error("s3a_dagpass_run_tables: out of device memory"); return S3A_ENOMEM; }
+            if (!dp->mem.dev(dp->own_tab[z], ((size_t)10 * E + F + 16) * 4)) { s3a_set_error("s3a_dagpass_run_tables: out of device memory"); return S3A_ENOMEM; }
             int32_t *w = dp->own_tab[z];
             DagTab tb;
             tb.score = w; tb.pred = w + E; tb.lw0 = w + 2 * (size_t)E; tb.lw1 = w + 3 * (size_t)E; tb.wid = w + 4 * (size_t)E; tb.sf = w + 5 * (size_t)E;

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "s3a_internal.h"
+#include "s3a_hostmem.h"
 
 #define HIPCHK(expr)                                                              \
     do {                                                                          \
@@ -33,15 +34,15 @@ struct s3a_mgau_dev_s {
     int32_t *bstidx, *bstscr, *updatetime;  /* [S] */
     hipStream_t stream;
     /* scratch for the host-pointer API */
-    float *feat_buf;   size_t feat_cap;     /* padded [T][D4*4] */
-    int32_t *scr_buf;  size_t scr_cap;
-    int32_t *best_buf; size_t best_cap;
+    s3a_grow<float> feat_buf;               /* padded [T][D4*4]; the capacities are bytes */
+    s3a_grow<int32_t> scr_buf, best_buf;
     int32_t n_cu;
     hipEvent_t ev0, ev1;        /* s3a_stream_timer_* */
     /* the log-add table repacked for the frame-synchronous pass (k_score_frame_sync): 16-bit entries up to
      * hyb_head, 8-bit entries from there on (the values have dropped below 256): 38 KB instead of 58 */
     int32_t hyb_ok, hyb_head, hyb_bytes;
     uint8_t *hyb_tab;           /* device: [hyb_head uint16][tab_size - hyb_head uint8], padded to 16 bytes */
+    s3a_hostmem mem;            /* every device buffer above is its */
 };
 
 
@@ -101,7 +102,5 @@ gau_to_int(double dval, double f, double distfloor, int32_t mixw)
 }
 
 #define D4MAIN 10           /* ceil(39/4): the 1s_c_d_dd case gets the unrolled kernels */
-
-int32_t s3a_dev_grow(void **buf, size_t *cap, size_t need);
 
 #endif

@@ -99,8 +99,11 @@ extern "C" int32_t s3a_dev_download(void *d, const void *s, size_t n)
 }
 extern "C" int32_t s3a_dev_sync(void) { HIPCHK(hipDeviceSynchronize()); return S3A_OK; }
 
-extern "C" int32_t
-s3a_mgau_dev_create(s3a_mgau_model_t *g)
+#define DM(ptr, bytes) do { if (!d->mem.dev(ptr, bytes)) return S3A_EHIP; } while (0)
+
+/* (a failure leaves what was made so far to s3a_mgau_dev_create, which destroys it) */
+static int32_t
+mgau_dev_fill(s3a_mgau_model_t *g)
 {
     struct s3a_mgau_dev_s *d;
     int ndev = 0;
@@ -115,7 +118,7 @@ s3a_mgau_dev_create(s3a_mgau_model_t *g)
         s3a_set_error("%d components per senone: more than 64 is not supported", g->max_comp);
         return S3A_EUNSUP;
     }
-    d = (struct s3a_mgau_dev_s *)calloc(1, sizeof *d);
+    d = new s3a_mgau_dev_s();          /* (value-initialised) */
     g->dev = d;
     d->S = g->n_mgau;
     d->C = g->max_comp;
@@ -147,10 +150,8 @@ s3a_mgau_dev_create(s3a_mgau_model_t *g)
                 hl[gi] = g->lrd[(size_t)s * d->C + c];
                 hw[gi] = g->mixw[(size_t)s * d->C + c];
             }
-        HIPCHK(hipMalloc(&d->mean4, nv * sizeof(float4)));
-        HIPCHK(hipMalloc(&d->prec4, nv * sizeof(float4)));
-        HIPCHK(hipMalloc(&d->lrd, d->Gpad * sizeof(float)));
-        HIPCHK(hipMalloc(&d->mixw, d->Gpad * sizeof(int32_t)));
+        DM(d->mean4, nv * sizeof(float4)); DM(d->prec4, nv * sizeof(float4));
+        DM(d->lrd, d->Gpad * sizeof(float)); DM(d->mixw, d->Gpad * sizeof(int32_t));
         HIPCHK(hipMemcpy(d->mean4, hm.data(), nv * sizeof(float4), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d->prec4, hp.data(), nv * sizeof(float4), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d->lrd, hl.data(), d->Gpad * sizeof(float), hipMemcpyHostToDevice));
@@ -167,11 +168,11 @@ s3a_mgau_dev_create(s3a_mgau_model_t *g)
         if (lm->width <= 2) {
             std::vector<uint16_t> t(((size_t)lm->table_size + 7) & ~(size_t)7, 0);  /* 16-byte multiple */
             for (uint32_t i = 0; i < lm->table_size; i++) t[i] = (uint16_t)lm->table[i];
-            HIPCHK(hipMalloc(&d->tab16, t.size() * 2));
+            DM(d->tab16, t.size() * 2);
             HIPCHK(hipMemcpy(d->tab16, t.data(), t.size() * 2, hipMemcpyHostToDevice));
         }
         else {
-            HIPCHK(hipMalloc(&d->tab32, (size_t)lm->table_size * 4));
+            DM(d->tab32, (size_t)lm->table_size * 4);
             HIPCHK(hipMemcpy(d->tab32, lm->table, (size_t)lm->table_size * 4,
                              hipMemcpyHostToDevice));
         }
@@ -191,16 +192,22 @@ s3a_mgau_dev_create(s3a_mgau_model_t *g)
             std::vector<uint8_t> pk(bytes, 0);
             for (uint32_t i = 0; i < head && i < lm->table_size; i++) ((uint16_t *)pk.data())[i] = (uint16_t)lm->table[i];
             for (uint32_t i = head; i < lm->table_size; i++) pk[(size_t)head * 2 + (i - head)] = (uint8_t)lm->table[i];
-            HIPCHK(hipMalloc(&d->hyb_tab, bytes));
+            DM(d->hyb_tab, bytes);
             HIPCHK(hipMemcpy(d->hyb_tab, pk.data(), bytes, hipMemcpyHostToDevice));
             d->hyb_ok = 1; d->hyb_head = (int32_t)head; d->hyb_bytes = (int32_t)bytes;
         }
     }
-    HIPCHK(hipMalloc(&d->bstidx, d->S * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&d->bstscr, d->S * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&d->updatetime, d->S * sizeof(int32_t)));
+    DM(d->bstidx, d->S * sizeof(int32_t)); DM(d->bstscr, d->S * sizeof(int32_t)); DM(d->updatetime, d->S * sizeof(int32_t));
     HIPCHK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
     return s3a_mgau_reset_state(g);
+}
+
+extern "C" int32_t
+s3a_mgau_dev_create(s3a_mgau_model_t *g)
+{
+    const int32_t rc = mgau_dev_fill(g);
+    if (rc != S3A_OK) s3a_mgau_dev_destroy(g);
+    return rc;
 }
 
 /*
@@ -247,13 +254,10 @@ s3a_mgau_dev_destroy(s3a_mgau_model_t *g)
     struct s3a_mgau_dev_s *d = g->dev;
     if (!d)
         return;
-    hipFree(d->mean4); hipFree(d->prec4); hipFree(d->lrd); hipFree(d->mixw);
-    hipFree(d->tab16); hipFree(d->tab32); hipFree(d->hyb_tab);
-    hipFree(d->bstidx); hipFree(d->bstscr); hipFree(d->updatetime);
-    hipFree(d->feat_buf); hipFree(d->scr_buf); hipFree(d->best_buf);
+    d->mem.free_all();
     if (d->stream) hipStreamDestroy(d->stream);
     if (d->ev0) { hipEventDestroy(d->ev0); hipEventDestroy(d->ev1); }
-    free(d);
+    delete d;
     g->dev = NULL;
 }
 
@@ -748,19 +752,6 @@ s3a_mgau_score_frames_dev(s3a_mgau_model_t *g, const float *feat_dev, int32_t n_
                         stream ? (hipStream_t)stream : g->dev->stream);
 }
 
-int32_t
-s3a_dev_grow(void **buf, size_t *cap, size_t need)
-{
-    if (*cap >= need)
-        return S3A_OK;
-    if (*buf) hipFree(*buf);
-    *buf = NULL;
-    *cap = 0;
-    HIPCHK(hipMalloc(buf, need));
-    *cap = need;
-    return S3A_OK;
-}
-
 extern "C" int32_t
 s3a_mgau_score_frames(s3a_mgau_model_t *g, const float *feat, int32_t n_frames,
                       int32_t *senscr, int32_t *best)
@@ -780,17 +771,16 @@ s3a_mgau_score_frames(s3a_mgau_model_t *g, const float *feat, int32_t n_frames,
     d = g->dev;
     fb = (size_t)n_frames * d->D * sizeof(float);
     sb = (size_t)n_frames * d->S * sizeof(int32_t);
-    if ((rc = s3a_dev_grow((void **)&d->feat_buf, &d->feat_cap, fb)) != S3A_OK) return rc;
-    if ((rc = s3a_dev_grow((void **)&d->scr_buf, &d->scr_cap, sb)) != S3A_OK) return rc;
-    if ((rc = s3a_dev_grow((void **)&d->best_buf, &d->best_cap, (size_t)n_frames * 4)) != S3A_OK) return rc;
-    HIPCHK(hipMemcpyAsync(d->feat_buf, feat, fb, hipMemcpyHostToDevice, d->stream));
-    rc = launch_score(g, d->feat_buf, d->D, n_frames, d->scr_buf, best ? d->best_buf : NULL,
+    if (d->feat_buf.reserve(d->mem, S3A_GROW_DEV, fb, fb, 1) != S3A_OK || d->scr_buf.reserve(d->mem, S3A_GROW_DEV, sb, sb, 1) != S3A_OK
+        || d->best_buf.reserve(d->mem, S3A_GROW_DEV, (size_t)n_frames * 4, (size_t)n_frames * 4, 1) != S3A_OK) return S3A_EHIP;
+    HIPCHK(hipMemcpyAsync(d->feat_buf.d, feat, fb, hipMemcpyHostToDevice, d->stream));
+    rc = launch_score(g, d->feat_buf.d, d->D, n_frames, d->scr_buf.d, best ? d->best_buf.d : NULL,
                       d->stream);
     if (rc != S3A_OK)
         return rc;
-    HIPCHK(hipMemcpyAsync(senscr, d->scr_buf, sb, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipMemcpyAsync(senscr, d->scr_buf.d, sb, hipMemcpyDeviceToHost, d->stream));
     if (best)
-        HIPCHK(hipMemcpyAsync(best, d->best_buf, (size_t)n_frames * 4, hipMemcpyDeviceToHost,
+        HIPCHK(hipMemcpyAsync(best, d->best_buf.d, (size_t)n_frames * 4, hipMemcpyDeviceToHost,
                               d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     return S3A_OK;
@@ -920,7 +910,7 @@ s3a_mgau_eval(s3a_mgau_model_t *g, int32_t m, const int32_t *active_comp, const 
               int32_t fr, int32_t update_best_id)
 {
     struct s3a_mgau_dev_s *d;
-    int32_t n_active = 0, rc, result = S3A_LOGPROB_ZERO;
+    int32_t n_active = 0, result = S3A_LOGPROB_ZERO;
     float *dx;
     int32_t *dact = NULL, *dout;
     size_t need;
@@ -944,9 +934,9 @@ s3a_mgau_eval(s3a_mgau_model_t *g, int32_t m, const int32_t *active_comp, const 
         }
     /* scratch: [x: D floats][active: n ints][out: 1 int] in feat_buf */
     need = (size_t)(d->D + n_active + 2) * 4;
-    if ((rc = s3a_dev_grow((void **)&d->feat_buf, &d->feat_cap, need)) != S3A_OK)
+    if (d->feat_buf.reserve(d->mem, S3A_GROW_DEV, need, need, 1) != S3A_OK)
         return S3A_LOGPROB_ZERO;
-    dx = d->feat_buf;
+    dx = d->feat_buf.d;
     dout = (int32_t *)(dx + d->D);
     if (hipMemcpyAsync(dx, x, d->D * 4, hipMemcpyHostToDevice, d->stream) != hipSuccess)
         return S3A_LOGPROB_ZERO;

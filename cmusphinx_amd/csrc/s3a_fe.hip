@@ -43,9 +43,10 @@ struct s3a_fe_s {
     float *d_filt, *d_cos, *d_lifter;
     float sqrt_inv_n, sqrt_inv_2n;
     /* scratch for the host-pointer entry point */
-    int16_t *d_spch; size_t spch_cap;
-    float *d_cep; size_t cep_cap;
+    s3a_grow<int16_t> spch;
+    s3a_grow<float> cep;
     hipStream_t stream;
+    s3a_hostmem mem;            /* every device buffer above is its */
 };
 
 struct FeDev {
@@ -271,10 +272,9 @@ static float mel2hz(const FeWarp &w, float mel) { const float wd = (float)(700.0
 
 template <typename T>
 static int32_t
-upload(T **dst, const std::vector<T> &v)
+upload(s3a_hostmem &m, T **dst, const std::vector<T> &v)
 {
-    const size_t n = v.size() ? v.size() : 1;
-    if (hipMalloc((void **)dst, n * sizeof(T)) != hipSuccess) return S3A_EHIP;
+    if (!m.dev(*dst, v.size() * sizeof(T))) return S3A_EHIP;
     if (v.size() && hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return S3A_EHIP;
     return S3A_OK;
 }
@@ -297,14 +297,15 @@ s3a_fe_init(const s3a_fe_params_t *p)
         s3a_set_error("s3a_fe_init: bad -transform / -logspec / -frate / -nfilt / -ncep");
         return NULL;
     }
-    s3a_fe_t *fe = (s3a_fe_t *)calloc(1, sizeof *fe);
+    s3a_fe_t *fe = new s3a_fe_s();     /* (value-initialised) */
+    s3a_hostmem &m = fe->mem;
     fe->p = *p;
     fe->fft_order = order;
     fe->frame_shift = (int32_t)(p->samprate / (int16_t)p->frate + 0.5);
     fe->frame_size = (int32_t)(p->wlen * p->samprate + 0.5);
     if (fe->frame_size > p->nfft || fe->frame_size < 2 || fe->frame_shift < 1) {
         s3a_set_error("s3a_fe_init: frame size %d / shift %d do not fit -nfft %d", fe->frame_size, fe->frame_shift, p->nfft);
-        free(fe);
+        delete fe;
         return NULL;
     }
     fe->out_dim = p->logspec ? p->nfilt : p->ncep;
@@ -326,7 +327,7 @@ s3a_fe_init(const s3a_fe_params_t *p)
         melmin -= melbw; melmax += melbw;
         if (mel2hz(warp, melmin) < 0 || mel2hz(warp, melmax) > p->samprate / 2) {
             s3a_set_error("s3a_fe_init: -doublebw filter edges out of range (%f .. %f)", mel2hz(warp, melmin), mel2hz(warp, melmax));
-            free(fe);
+            delete fe;
             return NULL;
         }
     }
@@ -354,7 +355,7 @@ s3a_fe_init(const s3a_fe_params_t *p)
         if (sstart[i] < 0 || fwidth[i] < 0 || sstart[i] + fwidth[i] > nbin) {
             /* (the reference would index out of its arrays here: a filter bank that does not fit the FFT) */
             s3a_set_error("s3a_fe_init: mel filter %d does not fit the spectrum (edges %g .. %g Hz)", i, lo, hi);
-            free(fe);
+            delete fe;
             return NULL;
         }
         fstart[i] = (int16_t)coeff.size();
@@ -378,9 +379,9 @@ s3a_fe_init(const s3a_fe_params_t *p)
         for (int32_t i = 0; i < p->ncep; i++)
             lift[i] = (float)(1 + p->lifter / 2 * sin(i * M_PI / p->lifter));   /* (the reference's integer lifter / 2) */
 
-    if (upload(&fe->d_hamming, ham) || upload(&fe->d_cc, cc) || upload(&fe->d_ss, ss)
-        || upload(&fe->d_spec_start, sstart) || upload(&fe->d_filt_start, fstart) || upload(&fe->d_filt_width, fwidth)
-        || upload(&fe->d_filt, coeff) || upload(&fe->d_cos, cosine) || upload(&fe->d_lifter, lift)
+    if (upload(m, &fe->d_hamming, ham) || upload(m, &fe->d_cc, cc) || upload(m, &fe->d_ss, ss)
+        || upload(m, &fe->d_spec_start, sstart) || upload(m, &fe->d_filt_start, fstart) || upload(m, &fe->d_filt_width, fwidth)
+        || upload(m, &fe->d_filt, coeff) || upload(m, &fe->d_cos, cosine) || upload(m, &fe->d_lifter, lift)
         || hipStreamCreateWithFlags(&fe->stream, hipStreamNonBlocking) != hipSuccess) {
         s3a_set_error("s3a_fe_init: device allocation failed: %s", hipGetErrorString(hipGetLastError()));
         s3a_fe_free(fe);
@@ -393,12 +394,9 @@ extern "C" void
 s3a_fe_free(s3a_fe_t *fe)
 {
     if (!fe) return;
-    (void)hipFree(fe->d_hamming); (void)hipFree(fe->d_cc); (void)hipFree(fe->d_ss);
-    (void)hipFree(fe->d_spec_start); (void)hipFree(fe->d_filt_start); (void)hipFree(fe->d_filt_width);
-    (void)hipFree(fe->d_filt); (void)hipFree(fe->d_cos); (void)hipFree(fe->d_lifter);
-    (void)hipFree(fe->d_spch); (void)hipFree(fe->d_cep);
+    fe->mem.free_all();
     if (fe->stream) (void)hipStreamDestroy(fe->stream);
-    free(fe);
+    delete fe;
 }
 
 extern "C" int32_t s3a_fe_output_size(const s3a_fe_t *fe) { return fe ? fe->out_dim : S3A_EINVAL; }
@@ -459,11 +457,11 @@ s3a_fe_process_utt(s3a_fe_t *fe, const int16_t *spch, int64_t nsamps, float *cep
     if (n > max_frames) { s3a_set_error("s3a_fe_process_utt: %d frames, room for %d", n, max_frames); return S3A_EINVAL; }
     if (n == 0) return S3A_OK;
     int32_t rc;
-    if ((rc = s3a_dev_grow((void **)&fe->d_spch, &fe->spch_cap, (size_t)nsamps * 2)) != S3A_OK) return rc;
-    if ((rc = s3a_dev_grow((void **)&fe->d_cep, &fe->cep_cap, (size_t)n * fe->out_dim * 4)) != S3A_OK) return rc;
-    HIPCHK(hipMemcpyAsync(fe->d_spch, spch, (size_t)nsamps * 2, hipMemcpyHostToDevice, fe->stream));
-    if ((rc = s3a_fe_process_utt_dev(fe, fe->d_spch, nsamps, fe->d_cep, max_frames, n_frames, fe->stream)) != S3A_OK) return rc;
-    HIPCHK(hipMemcpyAsync(cep, fe->d_cep, (size_t)n * fe->out_dim * 4, hipMemcpyDeviceToHost, fe->stream));
+    if (fe->spch.reserve(fe->mem, S3A_GROW_DEV, (size_t)nsamps, (size_t)nsamps) != S3A_OK
+        || fe->cep.reserve(fe->mem, S3A_GROW_DEV, (size_t)n * fe->out_dim, (size_t)n * fe->out_dim) != S3A_OK) return S3A_EHIP;
+    HIPCHK(hipMemcpyAsync(fe->spch.d, spch, (size_t)nsamps * 2, hipMemcpyHostToDevice, fe->stream));
+    if ((rc = s3a_fe_process_utt_dev(fe, fe->spch.d, nsamps, fe->cep.d, max_frames, n_frames, fe->stream)) != S3A_OK) return rc;
+    HIPCHK(hipMemcpyAsync(cep, fe->cep.d, (size_t)n * fe->out_dim * 4, hipMemcpyDeviceToHost, fe->stream));
     HIPCHK(hipStreamSynchronize(fe->stream));
     return S3A_OK;
 }

@@ -111,9 +111,9 @@ s3a_feat_1s_c_d_dd_dev(const float *cep, int32_t n_frames, int32_t cepsize, int3
         return S3A_EINVAL;
     }
     hipStream_t st = (hipStream_t)stream;
+    s3a_hostmem tmp;
     float *cep_d = NULL, *stats = NULL;
-    HIPCHK(hipMalloc((void **)&cep_d, (size_t)n_frames * cepsize * 4));
-    HIPCHK(hipMalloc((void **)&stats, (size_t)(2 * cepsize + 1) * 4));
+    if (!tmp.dev(cep_d, (size_t)n_frames * cepsize * 4) || !tmp.dev(stats, (size_t)(2 * cepsize + 1) * 4)) return S3A_EHIP;
     HIPCHK(hipMemcpyAsync(cep_d, cep, (size_t)n_frames * cepsize * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_feat_stats, dim3(1), dim3(256), 0, st, cep_d, n_frames, cepsize, cmn_current, varnorm,
                        agc_max, stats);
@@ -121,7 +121,6 @@ s3a_feat_1s_c_d_dd_dev(const float *cep, int32_t n_frames, int32_t cepsize, int3
                        cepsize, cmn_current, varnorm, agc_max, stats, feat_dev, feat_stride);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
-    (void)hipFree(cep_d); (void)hipFree(stats);
     return S3A_OK;
 }
 
@@ -131,14 +130,14 @@ s3a_feat_1s_c_d_dd(const float *cep, int32_t n_frames, int32_t cepsize, int32_t 
                    int32_t agc_max, float *feat)
 {
     if (!feat || n_frames <= 0 || cepsize <= 0) return S3A_EINVAL;
+    s3a_hostmem tmp;
     float *fd = NULL;
-    HIPCHK(hipMalloc((void **)&fd, (size_t)n_frames * 3 * cepsize * 4));
+    if (!tmp.dev(fd, (size_t)n_frames * 3 * cepsize * 4)) return S3A_EHIP;
     int32_t rc = s3a_feat_1s_c_d_dd_dev(cep, n_frames, cepsize, cmn_current, varnorm, agc_max, fd, 3 * cepsize, NULL);
     if (rc == S3A_OK && hipMemcpy(feat, fd, (size_t)n_frames * 3 * cepsize * 4, hipMemcpyDeviceToHost) != hipSuccess) {
         s3a_set_error("s3a_feat_1s_c_d_dd: read-back failed");
         rc = S3A_EHIP;
     }
-    (void)hipFree(fd);
     return rc;
 }
 
@@ -164,12 +163,12 @@ audio_to_feat_dev(s3a_fe_t *fe, const int16_t *spch, int64_t nsamps, int32_t dro
     if (cs <= 0 || cs > FMAXC) { s3a_set_error("s3a_audio_to_feat_dev: %d cepstral dimensions (1..%d)", cs, FMAXC); return S3A_EINVAL; }
     if (n <= 0) { s3a_set_error("s3a_audio_to_feat_dev: %lld samples are less than one frame of %d", (long long)nsamps, fsize); return S3A_EINVAL; }
     hipStream_t st = (hipStream_t)s3a_fe_stream(fe);
+    s3a_hostmem tmp;            /* (what is still its at the return is freed there: after the synchronisation) */
     int16_t *spch_d = NULL;
     float *cep_d = NULL, *out = NULL;
     const size_t row = (size_t)*feat_stride, out_floats = (size_t)n * row + 5 * FMAXC + 8;     /* (+ the statistics behind the rows) */
     int32_t rc = S3A_OK, k = 0;
-    if (hipMalloc((void **)&spch_d, (size_t)nsamps * 2) != hipSuccess || hipMalloc((void **)&cep_d, (size_t)n_all * cs * 4) != hipSuccess
-        || hipMalloc((void **)&out, out_floats * 4) != hipSuccess) {
+    if (!tmp.dev(spch_d, (size_t)nsamps * 2) || !tmp.dev(cep_d, (size_t)n_all * cs * 4) || !tmp.dev(out, out_floats * 4)) {
         s3a_set_error("s3a_audio_to_feat_dev: out of device memory");
         rc = S3A_ENOMEM;
     }
@@ -188,9 +187,8 @@ audio_to_feat_dev(s3a_fe_t *fe, const int16_t *spch, int64_t nsamps, int32_t dro
     }
     if (rc == S3A_OK && prior_sum && hipMemcpyAsync(prior_sum, out + (size_t)n * row + 4 * FMAXC, (size_t)cs * 4, hipMemcpyDeviceToHost, st) != hipSuccess) rc = S3A_EHIP;
     if (hipStreamSynchronize(st) != hipSuccess && rc == S3A_OK) rc = S3A_EHIP;
-    if (spch_d) (void)hipFree(spch_d);
-    if (cep_d) (void)hipFree(cep_d);
-    if (rc != S3A_OK) { if (out) (void)hipFree(out); return rc; }
+    if (rc != S3A_OK) return rc;
+    tmp.forget(out);            /* the caller's now */
     *feat_dev_out = out;
     return S3A_OK;
 }
@@ -245,9 +243,9 @@ s3a_feat_lda_dev(float **feat_dev, int32_t n_frames, int32_t *feat_stride, const
     }
     hipStream_t st = (hipStream_t)stream;
     const int32_t os = 4 * ((out_dim + 3) / 4);
+    s3a_hostmem tmp;
     float *lda_d = NULL, *out = NULL;
-    if (hipMalloc((void **)&lda_d, (size_t)out_dim * in_dim * 4) != hipSuccess || hipMalloc((void **)&out, ((size_t)n_frames * os + 8) * 4) != hipSuccess) {
-        if (lda_d) (void)hipFree(lda_d);
+    if (!tmp.dev(lda_d, (size_t)out_dim * in_dim * 4) || !tmp.dev(out, ((size_t)n_frames * os + 8) * 4)) {
         s3a_set_error("s3a_feat_lda_dev: out of device memory");
         return S3A_ENOMEM;
     }
@@ -258,9 +256,9 @@ s3a_feat_lda_dev(float **feat_dev, int32_t n_frames, int32_t *feat_stride, const
         if (hipGetLastError() != hipSuccess) rc = S3A_EHIP;
     }
     if (hipStreamSynchronize(st) != hipSuccess && rc == S3A_OK) rc = S3A_EHIP;
-    (void)hipFree(lda_d);
-    if (rc != S3A_OK) { (void)hipFree(out); return rc; }
-    (void)hipFree(*feat_dev);
+    if (rc != S3A_OK) return rc;
+    tmp.forget(out);            /* the caller's now, in place of the rows it handed in */
+    tmp.release(*feat_dev);
     *feat_dev = out; *feat_stride = os;
     return S3A_OK;
 }

@@ -41,6 +41,7 @@ struct s3a_hmm_batch_s {
     int16_t *sseq;      /* [n_sseq][ne] */
     int32_t *senscr;    /* [n_sen] */
     hipStream_t stream;
+    s3a_hostmem mem;    /* every device buffer above is its */
 };
 
 typedef HmmRegsT<int64_t> HmmRegs;
@@ -312,17 +313,14 @@ s3a_hmm_batch_init(int32_t n_hmm, int32_t n_emit_state, const s3a_tmat_t *tmat,
             s3a_set_error("s3a_hmm_batch_init: sseq entry %d out of range", i);
             return NULL;
         }
-    b = (s3a_hmm_batch_t *)calloc(1, sizeof *b);
+    b = new s3a_hmm_batch_s();
+    s3a_hostmem &m = b->mem;
     b->n = n_hmm; b->ne = n_emit_state; b->n_tmat = tmat->n_tmat; b->n_sseq = n_sseq; b->n_sen = n_sen;
     size_t tpn = (size_t)tmat->n_tmat * n_emit_state * (n_emit_state + 1);
-    if (hipMalloc(&b->score, 4 * NS * n) != hipSuccess || hipMalloc(&b->hist, 8 * NS * n) != hipSuccess
-        || hipMalloc(&b->out_score, 4 * n) != hipSuccess || hipMalloc(&b->out_hist, 8 * n) != hipSuccess
-        || hipMalloc(&b->bestscore, 4 * n) != hipSuccess || hipMalloc(&b->ssid, 4 * n) != hipSuccess
-        || hipMalloc(&b->mpx_ssid, 4 * NS * n) != hipSuccess || hipMalloc(&b->tmatid, 4 * n) != hipSuccess
-        || hipMalloc(&b->frame, 4 * n) != hipSuccess || hipMalloc(&b->ret, 4 * n) != hipSuccess
-        || hipMalloc(&b->mpx, n) != hipSuccess || hipMalloc(&b->tp, 4 * tpn) != hipSuccess
-        || hipMalloc(&b->sseq, 2 * (size_t)n_sseq * n_emit_state) != hipSuccess
-        || hipMalloc(&b->senscr, 4 * (size_t)n_sen) != hipSuccess
+    if (!m.dev(b->score, 4 * NS * n) || !m.dev(b->hist, 8 * NS * n) || !m.dev(b->out_score, 4 * n) || !m.dev(b->out_hist, 8 * n)
+        || !m.dev(b->bestscore, 4 * n) || !m.dev(b->ssid, 4 * n) || !m.dev(b->mpx_ssid, 4 * NS * n) || !m.dev(b->tmatid, 4 * n)
+        || !m.dev(b->frame, 4 * n) || !m.dev(b->ret, 4 * n) || !m.dev(b->mpx, n) || !m.dev(b->tp, 4 * tpn)
+        || !m.dev(b->sseq, 2 * (size_t)n_sseq * n_emit_state) || !m.dev(b->senscr, 4 * (size_t)n_sen)
         || hipMemcpy(b->tp, tmat->tp, 4 * tpn, hipMemcpyHostToDevice) != hipSuccess
         || hipMemcpy(b->sseq, sseq, 2 * (size_t)n_sseq * n_emit_state, hipMemcpyHostToDevice) != hipSuccess
         || hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -337,24 +335,21 @@ extern "C" void
 s3a_hmm_batch_free(s3a_hmm_batch_t *b)
 {
     if (!b) return;
-    (void)hipFree(b->score); (void)hipFree(b->hist); (void)hipFree(b->out_score);
-    (void)hipFree(b->out_hist); (void)hipFree(b->bestscore); (void)hipFree(b->ssid);
-    (void)hipFree(b->mpx_ssid); (void)hipFree(b->tmatid); (void)hipFree(b->frame);
-    (void)hipFree(b->ret); (void)hipFree(b->mpx); (void)hipFree(b->tp); (void)hipFree(b->sseq);
-    (void)hipFree(b->senscr);
+    b->mem.free_all();
     if (b->stream) (void)hipStreamDestroy(b->stream);
-    free(b);
+    delete b;
 }
 
 extern "C" int32_t
 s3a_hmm_batch_clear(s3a_hmm_batch_t *b, const int32_t *idx, int32_t n)
 {
+    s3a_hostmem tmp;
     int32_t *d_idx = NULL;
     if (!b) return S3A_EINVAL;
     if (idx == NULL) n = b->n;
     if (n <= 0) return S3A_OK;
     if (idx) {
-        HIPCHK(hipMalloc(&d_idx, 4 * (size_t)n));
+        if (!tmp.dev(d_idx, 4 * (size_t)n)) return S3A_EHIP;
         HIPCHK(hipMemcpyAsync(d_idx, idx, 4 * (size_t)n, hipMemcpyHostToDevice, b->stream));
     }
     hipLaunchKernelGGL(k_hmm_clear, dim3((n + 255) / 256), dim3(256), 0, b->stream, b->n, b->ne,
@@ -362,7 +357,6 @@ s3a_hmm_batch_clear(s3a_hmm_batch_t *b, const int32_t *idx, int32_t n)
                        b->frame);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(b->stream));
-    if (d_idx) (void)hipFree(d_idx);
     return S3A_OK;
 }
 
@@ -395,6 +389,7 @@ extern "C" int32_t
 s3a_hmm_batch_enter(s3a_hmm_batch_t *b, const int32_t *idx, const int32_t *score,
                     const int64_t *histid, int32_t n, int32_t frame)
 {
+    s3a_hostmem tmp;
     int32_t *d_idx, *d_scr;
     int64_t *d_hid;
     if (!b || n < 0 || (n && (!idx || !score || !histid))) return S3A_EINVAL;
@@ -404,9 +399,7 @@ s3a_hmm_batch_enter(s3a_hmm_batch_t *b, const int32_t *idx, const int32_t *score
             s3a_set_error("s3a_hmm_batch_enter: index out of range");
             return S3A_EINVAL;
         }
-    HIPCHK(hipMalloc(&d_idx, 4 * (size_t)n));
-    HIPCHK(hipMalloc(&d_scr, 4 * (size_t)n));
-    HIPCHK(hipMalloc(&d_hid, 8 * (size_t)n));
+    if (!tmp.dev(d_idx, 4 * (size_t)n) || !tmp.dev(d_scr, 4 * (size_t)n) || !tmp.dev(d_hid, 8 * (size_t)n)) return S3A_EHIP;
     HIPCHK(hipMemcpyAsync(d_idx, idx, 4 * (size_t)n, hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipMemcpyAsync(d_scr, score, 4 * (size_t)n, hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipMemcpyAsync(d_hid, histid, 8 * (size_t)n, hipMemcpyHostToDevice, b->stream));
@@ -414,7 +407,6 @@ s3a_hmm_batch_enter(s3a_hmm_batch_t *b, const int32_t *idx, const int32_t *score
                        d_scr, d_hid, n, frame, b->score, b->hist, b->frame);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(b->stream));
-    (void)hipFree(d_idx); (void)hipFree(d_scr); (void)hipFree(d_hid);
     return S3A_OK;
 }
 

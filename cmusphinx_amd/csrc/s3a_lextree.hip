@@ -488,7 +488,7 @@ k_fill_i32(int32_t *p, int32_t v, int32_t n)
 /* ------------------------------------------------------------------ */
 /* host side                                                           */
 /* ------------------------------------------------------------------ */
-#define DMALLOC(ptr, bytes) HIPCHK(hipMalloc((void **)&(ptr), (bytes) ? (bytes) : 4))
+#define DMALLOC(ptr, bytes) do { if (!ls->mem.dev(ptr, bytes)) return S3A_EHIP; } while (0)
 
 static int32_t
 fill(s3a_lexsearch_t *ls, int32_t *p, int32_t v, int32_t n)
@@ -545,7 +545,7 @@ alloc_state(s3a_lexsearch_t *ls)
     DMALLOC(ls->d_calls, (size_t)2 * 4096 * 4);
     DMALLOC(ls->d_ent, (size_t)2 * ls->ent_cap * 4); DMALLOC(ls->d_eflag, (size_t)ls->ent_cap * 4);
     DMALLOC(ls->d_first, (size_t)N * 4); DMALLOC(ls->d_key, (size_t)N * 8);
-    HIPCHK(hipHostMalloc((void **)&ls->h_pin, (size_t)(8 * n_tree + 16) * 4));
+    if (!ls->mem.pin(ls->h_pin, (size_t)(8 * n_tree + 16) * 4)) return S3A_EHIP;
     DMALLOC(ls->d_thr, 8 * 4);
     DMALLOC(ls->d_done, 4 * 4);
     HIPCHK(hipMemset(ls->d_done, 0, 16));
@@ -557,8 +557,8 @@ alloc_state(s3a_lexsearch_t *ls)
     HIPCHK(hipMemset(ls->d_key, 0, (size_t)N * 8));
     DMALLOC(ls->d_pack, (size_t)(6 * n_tree + 16 + 3 * ls->pack_max_exits) * 4);
     /* (coherent: k_dec_scan writes the frame record here directly; the host reads it after the event behind that kernel) */
-    HIPCHK(hipHostMalloc((void **)&ls->h_pack, (size_t)(6 * n_tree + 16 + 3 * ls->pack_max_exits) * 4, hipHostMallocCoherent));
-    HIPCHK(hipHostMalloc((void **)&ls->h_ring, (size_t)8 * (2 * 4096 + 2 * ls->ent_cap) * 4));
+    if (!ls->mem.pin(ls->h_pack, (size_t)(6 * n_tree + 16 + 3 * ls->pack_max_exits) * 4, hipHostMallocCoherent)
+        || !ls->mem.pin(ls->h_ring, (size_t)8 * (2 * 4096 + 2 * ls->ent_cap) * 4)) return S3A_EHIP;
     HIPCHK(hipEventCreateWithFlags(&ls->ev_pack, hipEventDisableTiming));
     return S3A_OK;
 }
@@ -767,20 +767,13 @@ extern "C" s3a_lexsearch_t *
 s3a_lexsearch_clone(const s3a_lexsearch_t *proto, void *stream)
 {
     if (!proto) return NULL;
-    s3a_lexsearch_t *ls = new s3a_lexsearch_s(*proto);         /* host fields + static device pointers */
-    ls->is_clone = 1;
+    s3a_lexsearch_t *ls = new s3a_lexsearch_s();       /* value-initialised: the state half starts at zero */
+    *static_cast<s3a_lextrees_s *>(ls) = *proto;        /* host tables + static device pointers (borrowed) */
+    ls->nnxt_t = proto->nnxt_t;                         /* (as a copy of the whole object brought it) */
     ls->opt_calls_by_copy = s3a_variants()->calls_by_copy != 0; ls->opt_scan_chained = s3a_variants()->scan_chained != 0;
-    /* everything alloc_state sets must not alias proto's */
-    ls->d_sc = ls->d_hist = ls->d_outs = ls->d_outh = ls->d_bests = ls->d_frame = ls->d_pos = ls->d_posf = NULL;
-    ls->d_act[0] = ls->d_act[1] = ls->d_nact[0] = ls->d_nact[1] = ls->d_cand = ls->d_ncand = ls->d_candf = NULL;
-    ls->d_turn = ls->d_selfemit = ls->d_cnt = ls->d_best = ls->d_exit = ls->d_nexit = ls->d_calls = NULL;
-    ls->d_ent = ls->d_eflag = ls->d_first = ls->d_thr = ls->d_done = ls->d_hbin = ls->d_pstamp = NULL;
-    ls->d_ctot = ls->d_n0 = ls->d_pack = NULL; ls->d_key = NULL; ls->d_poswid = ls->d_posout = NULL; ls->d_scan_agg = ls->d_scan_pre = NULL; ls->d_scan_flag = NULL;
-    ls->h_pin = ls->h_pack = ls->h_ring = NULL; ls->ev_pack = NULL; ls->ring_slot = 0; ls->cur = 0;
     if (stream) { ls->stream = (hipStream_t)stream; ls->own_stream = 0; }
     else if (hipStreamCreateWithFlags(&ls->stream, hipStreamNonBlocking) != hipSuccess) {
         s3a_set_error("s3a_lexsearch_clone: stream creation failed");
-        ls->own_stream = 0;
         s3a_lexsearch_free(ls);
         return NULL;
     }
@@ -796,26 +789,7 @@ extern "C" void
 s3a_lexsearch_free(s3a_lexsearch_t *ls)
 {
     if (!ls) return;
-    int32_t **statics[] = { &ls->d_node_base, &ls->d_ssid, &ls->d_tmatid, &ls->d_wid, &ls->d_prob,
-        &ls->d_child_off, &ls->d_child, &ls->d_par_off, &ls->d_par, &ls->d_rootlist, &ls->d_tp,
-        &ls->d_comstate_off, &ls->d_tree_of, &ls->d_rootnodes, &ls->d_ps, &ls->d_psof_off, &ls->d_psof, &ls->d_psmem_off, &ls->d_psmem };
-    int32_t **state[] = { &ls->d_sc,            /* (d_hist, d_outs, d_outh, d_bests, d_frame point into d_sc's records) */
-        &ls->d_pos, &ls->d_act[0], &ls->d_act[1], &ls->d_nact[0],
-        &ls->d_nact[1], &ls->d_cand, &ls->d_ncand, &ls->d_candf, &ls->d_turn, &ls->d_selfemit,
-        &ls->d_cnt, &ls->d_best, &ls->d_exit, &ls->d_nexit, &ls->d_calls, &ls->d_ent, &ls->d_eflag,
-        &ls->d_first, &ls->d_thr, &ls->d_pack, &ls->d_done, &ls->d_hbin, &ls->d_ctot, &ls->d_n0, &ls->d_pstamp,
-        &ls->d_poswid, &ls->d_posout, &ls->d_scan_flag };
-    for (auto p : state) (void)hipFree(*p);
-    (void)hipFree(ls->d_scan_agg); (void)hipFree(ls->d_scan_pre);
-    (void)hipFree(ls->d_key);
-    if (!ls->is_clone) {                /* a clone borrows its prototype's static arrays */
-        for (auto p : statics) (void)hipFree(*p);
-        (void)hipFree(ls->d_comp); (void)hipFree(ls->d_sseq); (void)hipFree(ls->d_comsseq);
-        (void)hipFree(ls->d_comstate);
-    }
-    if (ls->h_pin) (void)hipHostFree(ls->h_pin);
-    if (ls->h_pack) (void)hipHostFree(ls->h_pack);
-    if (ls->h_ring) (void)hipHostFree(ls->h_ring);
+    ls->mem.free_all();                 /* (a clone's owner never recorded the static arrays it borrows) */
     if (ls->ev_pack) (void)hipEventDestroy(ls->ev_pack);
     if (ls->own_stream && ls->stream) (void)hipStreamDestroy(ls->stream);
     delete ls;

@@ -45,6 +45,7 @@ struct s3a_ms_dev_s {
     int32_t *dist, *dist_id, *scr, *best;
     int32_t *scr_h, *best_h;        /* pinned */
     hipStream_t stream;
+    s3a_hostmem mem;                /* every device / pinned buffer above is its */
 };
 
 struct LogAdd32 {
@@ -160,10 +161,11 @@ k_ms_norm(int32_t n_sen, const uint8_t *__restrict__ sen_active, const int32_t *
 }
 
 /* ------------------------------------------------------------------ */
-#define DM(ptr, bytes) HIPCHK(hipMalloc((void **)&(ptr), (bytes) ? (bytes) : 4))
+#define DM(ptr, bytes) do { if (!dv->mem.dev(ptr, bytes)) return S3A_EHIP; } while (0)
 
-extern "C" int32_t
-s3a_ms_dev_create(s3a_ms_mgau_t *ms)
+/* (a failure leaves what was made so far to s3a_ms_dev_create, which destroys it) */
+static int32_t
+ms_dev_fill(s3a_ms_mgau_t *ms)
 {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -177,8 +179,7 @@ s3a_ms_dev_create(s3a_ms_mgau_t *ms)
         return S3A_EUNSUP;
     }
     if (ms->veclen * 4 > 48 * 1024) { s3a_set_error("s3a_ms_mgau_init: feature vector too long"); return S3A_EUNSUP; }
-    s3a_ms_dev_s *dv = new s3a_ms_dev_s();
-    memset(dv, 0, sizeof *dv);
+    s3a_ms_dev_s *dv = new s3a_ms_dev_s();     /* (value-initialised) */
     ms->dev = dv;
     dv->P = P;
     const int32_t M = ms->n_mgau, F = ms->n_feat, nd = ms->n_density, D = ms->veclen, S = ms->n_sen;
@@ -203,8 +204,7 @@ s3a_ms_dev_create(s3a_ms_mgau_t *ms)
     DM(dv->sen_active, (size_t)S); DM(dv->mgau_active, (size_t)M); DM(dv->feat, (size_t)D * 4);
     DM(dv->dist, (size_t)M * F * ms->topn * 4); DM(dv->dist_id, (size_t)M * F * ms->topn * 4);
     DM(dv->scr, (size_t)S * 4); DM(dv->best, 4);
-    HIPCHK(hipHostMalloc((void **)&dv->scr_h, (size_t)S * 4));
-    HIPCHK(hipHostMalloc((void **)&dv->best_h, 4));
+    if (!dv->mem.pin(dv->scr_h, (size_t)S * 4) || !dv->mem.pin(dv->best_h, 4)) return S3A_EHIP;
     HIPCHK(hipMemcpy(dv->meanT, mt.data(), nT * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dv->precT, pt.data(), nT * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dv->det, dt.data(), dt.size() * 4, hipMemcpyHostToDevice));
@@ -228,16 +228,20 @@ s3a_ms_dev_create(s3a_ms_mgau_t *ms)
     return S3A_OK;
 }
 
+extern "C" int32_t
+s3a_ms_dev_create(s3a_ms_mgau_t *ms)
+{
+    const int32_t rc = ms_dev_fill(ms);
+    if (rc != S3A_OK) s3a_ms_dev_destroy(ms);
+    return rc;
+}
+
 extern "C" void
 s3a_ms_dev_destroy(s3a_ms_mgau_t *ms)
 {
     s3a_ms_dev_s *dv = ms ? ms->dev : NULL;
     if (!dv) return;
-    void *ptrs[] = { dv->meanT, dv->precT, dv->det, dv->featlen, dv->featoff, dv->pdf, dv->mgau, dv->tab,
-                     dv->sen_active, dv->mgau_active, dv->feat, dv->dist, dv->dist_id, dv->scr, dv->best };
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (dv->scr_h) (void)hipHostFree(dv->scr_h);
-    if (dv->best_h) (void)hipHostFree(dv->best_h);
+    dv->mem.free_all();
     if (dv->stream) (void)hipStreamDestroy(dv->stream);
     delete dv;
     ms->dev = NULL;

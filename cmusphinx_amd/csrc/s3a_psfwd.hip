@@ -1444,8 +1444,7 @@ k_psf_mark_ready(int32_t *ready, int32_t n)
 struct s3a_psfwd_s {
     PsfModel M;
     int32_t n_lanes, n_sseq, n_tmat;
-    std::vector<void *> dev_static;         /* model arrays on the device */
-    std::vector<void *> dev_lane;           /* every lane's buffers */
+    s3a_hostmem mem;                        /* every device buffer of the engine is its: model arrays, lane slabs, staging, queue */
     std::vector<PsfLane> lanes_h;
     PsfLane *lanes_d;
     int32_t *lane_ids_d;
@@ -1458,26 +1457,24 @@ struct s3a_psfwd_s {
     std::vector<int32_t> t_frame, t_wid, t_bp, t_score, t_sidx, t_realwid, t_bss, t_idx;
     std::vector<uint8_t> t_valid;
     /* whole-utterance staging */
-    float *feat_d; size_t feat_cap;
-    int32_t *slot_row_d; size_t slot_cap;
-    int16_t *raw_d; size_t raw_cap;
+    s3a_grow<float> feat;
+    s3a_grow<int32_t> slot_row;
+    s3a_grow<int16_t> raw;
     int32_t win;
     /* the queue's per-utterance results */
-    int32_t *q_next_d, *q_nfr_d, *q_res_d, *q_order_d; long long *q_row0_d; s3a_psfwd_seg_t *q_seg_d;
-    size_t q_cap;
+    s3a_grow<int32_t> q_next, q_nfr, q_res, q_order; s3a_grow<long long> q_row0; s3a_grow<s3a_psfwd_seg_t> q_seg;   /* (one capacity) */
     int32_t q_n, q_seg_cap;
     std::vector<int32_t> q_res_h;
     std::vector<s3a_psfwd_seg_t> q_seg_h;
 };
 
 template <typename T> static T *
-up(s3a_psfwd_t *e, const T *src, size_t n, bool lane = false)
+up(s3a_psfwd_t *e, const T *src, size_t n)
 {
     T *d = NULL;
-    if (hipMalloc((void **)&d, (n ? n : 1) * sizeof(T)) != hipSuccess) return NULL;
+    if (!e->mem.dev(d, n * sizeof(T))) return NULL;
     if (src && n) { if (hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return NULL; }
-    else if (hipMemset(d, 0, (n ? n : 1) * sizeof(T)) != hipSuccess) return NULL;
-    (lane ? e->dev_lane : e->dev_static).push_back(d);
+    else if (hipMemset(d, 0, n ? n * sizeof(T) : 4) != hipSuccess) return NULL;
     return d;
 }
 
@@ -1487,20 +1484,12 @@ extern "C" void
 s3a_psfwd_free(s3a_psfwd_t *e)
 {
     if (!e) return;
-    for (void *p : e->dev_static) (void)hipFree(p);
-    for (void *p : e->dev_lane) (void)hipFree(p);
-    if (e->lanes_d) (void)hipFree(e->lanes_d);
-    if (e->lane_ids_d) (void)hipFree(e->lane_ids_d);
-    if (e->feat_d) (void)hipFree(e->feat_d);
-    if (e->slot_row_d) (void)hipFree(e->slot_row_d);
-    if (e->raw_d) (void)hipFree(e->raw_d);
-    { void *qp[] = { e->q_next_d, e->q_nfr_d, e->q_res_d, e->q_row0_d, e->q_seg_d, e->q_order_d }; for (void *q : qp) if (q) (void)hipFree(q); }
+    e->mem.free_all();
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->ev_mid) (void)hipEventDestroy(e->ev_mid);
     if (e->ev_sc) (void)hipEventDestroy(e->ev_sc);
     if (e->stream_sc) (void)hipStreamDestroy(e->stream_sc);
-    if (e->q_ready_d) (void)hipFree(e->q_ready_d);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -1519,12 +1508,9 @@ s3a_psfwd_init(const s3a_psfwd_desc_t *d, int32_t n_lanes, int32_t max_frames, i
     if (d->n_root > 32 * ROOTBITS_WORDS || d->n_sen > 32 * SENBITS_WORDS) { s3a_set_error("s3a_psfwd_init: %d roots / %d senones exceed the kernel's bit vectors", d->n_root, d->n_sen); return NULL; }
     if (d->n_1ph > NT) { s3a_set_error("s3a_psfwd_init: %d single-phone words exceed the kernel's %d", d->n_1ph, NT); return NULL; }
     if (max_frames > 32767) { s3a_set_error("s3a_psfwd_init: max_frames %d (the reference's frame numbers are int16)", max_frames); return NULL; }
-    s3a_psfwd_t *e = new s3a_psfwd_t();
-    e->lanes_d = NULL; e->lane_ids_d = NULL; e->stream = NULL; e->stream_sc = NULL; e->ev0 = e->ev1 = e->ev_sc = NULL; e->q_ready_d = NULL; e->last_ms = 0; e->last_score_ms = 0; e->ev_mid = NULL;
-    e->feat_d = NULL; e->feat_cap = 0; e->slot_row_d = NULL; e->slot_cap = 0; e->raw_d = NULL; e->raw_cap = 0; e->win = 0;
-    e->q_next_d = e->q_nfr_d = e->q_res_d = e->q_order_d = NULL; e->q_row0_d = NULL; e->q_seg_d = NULL; e->q_cap = 0; e->q_n = 0; e->q_seg_cap = 256;
+    s3a_psfwd_t *e = new s3a_psfwd_t();         /* (value-initialised: every member not set below is 0 / NULL) */
+    e->q_seg_cap = 256;
     PsfModel &M = e->M;
-    memset(&M, 0, sizeof(M));
     e->n_lanes = n_lanes;
     const int32_t NE = d->n_emit, W = d->n_words, n_ch = d->n_root + d->n_nonroot;
     M.n_ci = d->n_ci; M.sil_ci = d->sil_ci; M.n_emit = NE; M.n_sen = d->n_sen;
@@ -1600,7 +1586,7 @@ s3a_psfwd_init(const s3a_psfwd_desc_t *d, int32_t n_lanes, int32_t max_frames, i
 
     if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&e->ev0) != hipSuccess
         || hipStreamCreateWithFlags(&e->stream_sc, hipStreamNonBlocking) != hipSuccess
-        || hipEventCreateWithFlags(&e->ev_sc, hipEventDisableTiming) != hipSuccess || hipMalloc((void **)&e->q_ready_d, 4) != hipSuccess
+        || hipEventCreateWithFlags(&e->ev_sc, hipEventDisableTiming) != hipSuccess || !e->mem.dev(e->q_ready_d, 4)
         || hipEventCreate(&e->ev1) != hipSuccess || hipEventCreate(&e->ev_mid) != hipSuccess) { s3a_set_error("s3a_psfwd_init: stream / event creation failed"); s3a_psfwd_free(e); return NULL; }
     UP(M.sseq, d->sseq, (size_t)d->n_sseq * NE);
     UP(M.tp, d->tp, (size_t)d->n_tmat * NE * (NE + 1));
@@ -1654,18 +1640,15 @@ s3a_psfwd_init(const s3a_psfwd_desc_t *d, int32_t n_lanes, int32_t max_frames, i
         const size_t per_lane = layout(probe, (char *)NULL);
         for (int32_t z = 0; z < n_lanes; z++) {
             char *slab = NULL;
-            if (hipMalloc((void **)&slab, per_lane) != hipSuccess || hipMemset(slab, 0, per_lane) != hipSuccess) {
-                if (slab) (void)hipFree(slab);
+            if (!e->mem.dev(slab, per_lane) || hipMemset(slab, 0, per_lane) != hipSuccess) {
                 s3a_set_error("s3a_psfwd_init: device allocation failed (lane %d: %zu bytes)", z, per_lane);
                 s3a_psfwd_free(e);
                 return NULL;
             }
-            e->dev_lane.push_back(slab);
             (void)layout(e->lanes_h[z], slab);
         }
     }
-    if (hipMalloc((void **)&e->lanes_d, sizeof(PsfLane) * n_lanes) != hipSuccess
-        || hipMalloc((void **)&e->lane_ids_d, sizeof(int32_t) * n_lanes) != hipSuccess
+    if (!e->mem.dev(e->lanes_d, sizeof(PsfLane) * n_lanes) || !e->mem.dev(e->lane_ids_d, sizeof(int32_t) * n_lanes)
         || hipMemcpy(e->lanes_d, e->lanes_h.data(), sizeof(PsfLane) * n_lanes, hipMemcpyHostToDevice) != hipSuccess) {
         s3a_set_error("s3a_psfwd_init: device allocation failed (lane table)");
         s3a_psfwd_free(e);
@@ -1846,60 +1829,74 @@ s3a_psfwd_hyp(s3a_psfwd_t *e, int32_t lane, int32_t *out_score, s3a_psfwd_seg_t 
     return sc.n_seg;
 }
 
+/* The call steps s3a_psfwd_decode and s3a_psfwd_decode_queue share (fn: the caller's name in the error texts).
+ * The checks: at most max_utt utterances, a scorer of the search's senones, every utterance within max_frames and longer than the
+ * look-ahead; row0[z] = utterance z's first row of the batch's feature matrix, *total its rows, *longest the longest utterance. */
+static int32_t
+decode_check(const s3a_psfwd_t *e, const s3a_ps_mgau_t *scorer, const char *fn, int32_t n_utt, int32_t max_utt, const float *const *feat,
+             const int32_t *n_frames, std::vector<long long> &row0, size_t *total, int32_t *longest)
+{
+    if (!e || !scorer || !feat || !n_frames || n_utt < 1 || n_utt > max_utt) { s3a_set_error("%s: bad argument", fn); return S3A_EINVAL; }
+    const PsfModel &M = e->M;
+    if (s3a_ps_ms_mgau_n_sen(scorer) != M.n_sen) { s3a_set_error("%s: the scorer has %d senones, the search %d", fn, s3a_ps_ms_mgau_n_sen(scorer), M.n_sen); return S3A_EINVAL; }
+    *total = 0; *longest = 0;
+    row0.resize(n_utt);
+    for (int32_t z = 0; z < n_utt; z++) {
+        if (n_frames[z] < 0 || n_frames[z] > M.max_frames) { s3a_set_error("%s: utterance %d has %d frames (max_frames %d)", fn, z, n_frames[z], M.max_frames); return S3A_EINVAL; }
+        if (M.pl_window > 0 && n_frames[z] > 0 && n_frames[z] <= M.pl_window) {
+            s3a_set_error("%s: utterance %d has %d frames, not more than -pl_window %d", fn, z, n_frames[z], M.pl_window);
+            return S3A_EUNSUP;
+        }
+        row0[z] = (long long)*total; *total += n_frames[z];
+        *longest = n_frames[z] > *longest ? n_frames[z] : *longest;
+    }
+    return S3A_OK;
+}
+
+/* room for n_feat floats of features (+ one), n_slot feature-row numbers and n_raw senone scores */
+static int32_t
+decode_reserve(s3a_psfwd_t *e, size_t n_feat, size_t n_slot, size_t n_raw)
+{
+    if (e->feat.reserve(e->mem, S3A_GROW_DEV, n_feat, n_feat, 4, 4) != S3A_OK || e->slot_row.reserve(e->mem, S3A_GROW_DEV, n_slot, n_slot) != S3A_OK
+        || e->raw.reserve(e->mem, S3A_GROW_DEV, n_raw, n_raw) != S3A_OK) return S3A_EHIP;
+    return S3A_OK;
+}
+
+/* the utterances' features, rows of D floats, to their rows of e->feat */
+static int32_t
+decode_upload_feat(s3a_psfwd_t *e, int32_t D, int32_t n_utt, const float *const *feat, const int32_t *n_frames, const std::vector<long long> &row0)
+{
+    for (int32_t z = 0; z < n_utt; z++)
+        if (n_frames[z]) HIPCHK(hipMemcpyAsync(e->feat.d + (size_t)row0[z] * D, feat[z], (size_t)n_frames[z] * D * 4, hipMemcpyHostToDevice, e->stream));
+    return S3A_OK;
+}
+
 extern "C" int32_t
 s3a_psfwd_decode(s3a_psfwd_t *e, s3a_ps_mgau_t *scorer, int32_t n_utt, const float *const *feat, const int32_t *n_frames,
                  int32_t compallsen, int32_t fresh)
 {
-    if (!e || !scorer || !feat || !n_frames || n_utt < 1 || n_utt > e->n_lanes) { s3a_set_error("s3a_psfwd_decode: bad argument"); return S3A_EINVAL; }
+    size_t total = 0;
+    int32_t longest = 0, rc;
+    std::vector<long long> row0;
+    if ((rc = decode_check(e, scorer, "s3a_psfwd_decode", n_utt, e ? e->n_lanes : 0, feat, n_frames, row0, &total, &longest)) != S3A_OK) return rc;
     const PsfModel &M = e->M;
     const int32_t D = s3a_ps_ms_mgau_veclen(scorer);
     int32_t W = e->win;
-    if (s3a_ps_ms_mgau_n_sen(scorer) != M.n_sen) { s3a_set_error("s3a_psfwd_decode: the scorer has %d senones, the search %d", s3a_ps_ms_mgau_n_sen(scorer), M.n_sen); return S3A_EINVAL; }
-    size_t total = 0;
-    int32_t longest = 0;
-    std::vector<size_t> row0(n_utt);
-    for (int32_t z = 0; z < n_utt; z++) {
-        if (n_frames[z] < 0 || n_frames[z] > M.max_frames) { s3a_set_error("s3a_psfwd_decode: utterance %d has %d frames (max_frames %d)", z, n_frames[z], M.max_frames); return S3A_EINVAL; }
-        if (M.pl_window > 0 && n_frames[z] > 0 && n_frames[z] <= M.pl_window) {
-            s3a_set_error("s3a_psfwd_decode: utterance %d has %d frames, not more than -pl_window %d", z, n_frames[z], M.pl_window);
-            return S3A_EUNSUP;
-        }
-        row0[z] = total; total += n_frames[z];
-        longest = n_frames[z] > longest ? n_frames[z] : longest;
-    }
-    if (e->feat_cap < total * D) {
-        if (e->feat_d) (void)hipFree(e->feat_d);
-        e->feat_d = NULL; e->feat_cap = 0;
-        HIPCHK(hipMalloc((void **)&e->feat_d, (total * D + 1) * 4));
-        e->feat_cap = total * D;
-    }
     /* every lane's senone scores of the WHOLE utterance before its search starts (int16 per senone and frame: 12 MB per
      * 10 s of a 6144-senone model): the lanes then run their utterances from the first frame to the last in ONE launch,
      * none waiting for another at window boundaries (a frame's cost varies several-fold along an utterance) */
     if (e->win <= 0 || M.pl_window > 0) W = longest > 0 ? longest : 1;      /* (the phone loop reads rows ahead of the search's: one window) */
     const size_t n_slots = (size_t)n_utt * W, n_windows = (size_t)(longest + W - 1) / W + 1;
-    if (e->slot_cap < n_slots * n_windows) {
-        if (e->slot_row_d) (void)hipFree(e->slot_row_d);
-        e->slot_row_d = NULL; e->slot_cap = 0;
-        HIPCHK(hipMalloc((void **)&e->slot_row_d, n_slots * n_windows * 4));
-        e->slot_cap = n_slots * n_windows;
-    }
-    if (e->raw_cap < n_slots * M.n_sen) {
-        if (e->raw_d) (void)hipFree(e->raw_d);
-        e->raw_d = NULL; e->raw_cap = 0;
-        HIPCHK(hipMalloc((void **)&e->raw_d, n_slots * M.n_sen * 2));
-        e->raw_cap = n_slots * M.n_sen;
-    }
-    for (int32_t z = 0; z < n_utt; z++)
-        if (n_frames[z]) HIPCHK(hipMemcpyAsync(e->feat_d + row0[z] * D, feat[z], (size_t)n_frames[z] * D * 4, hipMemcpyHostToDevice, e->stream));
+    if ((rc = decode_reserve(e, total * D, n_slots * n_windows, n_slots * M.n_sen)) != S3A_OK
+        || (rc = decode_upload_feat(e, D, n_utt, feat, n_frames, row0)) != S3A_OK) return rc;
     std::vector<int32_t> ids(n_utt);
     for (int32_t z = 0; z < n_utt; z++) {
         ids[z] = z;
-        e->lanes_h[z].raw = e->raw_d + (size_t)z * W * M.n_sen;
+        e->lanes_h[z].raw = e->raw.d + (size_t)z * W * M.n_sen;
         HIPCHK(hipMemcpyAsync((char *)e->lanes_h[z].sc + offsetof(PsfScalars, n_total), &n_frames[z], 4, hipMemcpyHostToDevice, e->stream));
     }
     HIPCHK(hipMemcpyAsync(e->lanes_d, e->lanes_h.data(), sizeof(PsfLane) * n_utt, hipMemcpyHostToDevice, e->stream));
-    int32_t rc = start_lanes(e, ids.data(), n_utt, fresh);
+    rc = start_lanes(e, ids.data(), n_utt, fresh);
     if (rc != S3A_OK) return rc;
     /* which feature row every (window, lane, frame of the window) slot scores; -1 = past the utterance's end */
     std::vector<int32_t> slot_row(n_slots * n_windows);
@@ -1909,10 +1906,10 @@ s3a_psfwd_decode(s3a_psfwd_t *e, s3a_ps_mgau_t *scorer, int32_t n_utt, const flo
                 const int32_t f = (int32_t)wi * W + t;
                 slot_row[wi * n_slots + (size_t)z * W + t] = f < n_frames[z] ? (int32_t)(row0[z] + f) : -1;
             }
-    HIPCHK(hipMemcpyAsync(e->slot_row_d, slot_row.data(), slot_row.size() * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->slot_row.d, slot_row.data(), slot_row.size() * 4, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipEventRecord(e->ev0, e->stream));
     for (int32_t f0 = 0, wi = 0; f0 < (longest > 0 ? longest : 1); f0 += W, wi++) {
-        rc = s3a_ps_score_slots_dev(scorer, e->feat_d, e->slot_row_d + (size_t)wi * n_slots, (int32_t)n_slots, e->raw_d, e->stream);
+        rc = s3a_ps_score_slots_dev(scorer, e->feat.d, e->slot_row.d + (size_t)wi * n_slots, (int32_t)n_slots, e->raw.d, e->stream);
         if (rc != S3A_OK) return rc;
         NEPL_LAUNCH(k_psf_window, dim3(n_utt), M, e->lanes_d, e->lane_ids_d, f0, W, compallsen, fresh ? 1 : 0);
         HIPCHK(hipGetLastError());
@@ -1945,72 +1942,45 @@ extern "C" int32_t
 s3a_psfwd_decode_queue(s3a_psfwd_t *e, s3a_ps_mgau_t *scorer, int32_t n_utt, const float *const *feat, const int32_t *n_frames,
                        int32_t compallsen)
 {
-    if (!e || !scorer || !feat || !n_frames || n_utt < 1) { s3a_set_error("s3a_psfwd_decode_queue: bad argument"); return S3A_EINVAL; }
+    size_t total = 0;
+    int32_t longest = 0, rc;
+    std::vector<long long> row0;
+    if ((rc = decode_check(e, scorer, "s3a_psfwd_decode_queue", n_utt, INT_MAX, feat, n_frames, row0, &total, &longest)) != S3A_OK) return rc;
     const PsfModel &M = e->M;
     const int32_t D = s3a_ps_ms_mgau_veclen(scorer);
-    if (s3a_ps_ms_mgau_n_sen(scorer) != M.n_sen) { s3a_set_error("s3a_psfwd_decode_queue: the scorer has %d senones, the search %d", s3a_ps_ms_mgau_n_sen(scorer), M.n_sen); return S3A_EINVAL; }
-    size_t total = 0;
-    std::vector<long long> row0(n_utt);
-    for (int32_t z = 0; z < n_utt; z++) {
-        if (n_frames[z] < 0 || n_frames[z] > M.max_frames) { s3a_set_error("s3a_psfwd_decode_queue: utterance %d has %d frames (max_frames %d)", z, n_frames[z], M.max_frames); return S3A_EINVAL; }
-        if (M.pl_window > 0 && n_frames[z] > 0 && n_frames[z] <= M.pl_window) {
-            s3a_set_error("s3a_psfwd_decode_queue: utterance %d has %d frames, not more than -pl_window %d", z, n_frames[z], M.pl_window);
-            return S3A_EUNSUP;
-        }
-        row0[z] = (long long)total; total += n_frames[z];
+    if ((rc = decode_reserve(e, total * D, total + 1, (total + 1) * M.n_sen)) != S3A_OK) return rc;
+    {
+        /* the six queue arrays under one capacity, the utterances (q_next is one word whatever that is) */
+        s3a_hostmem &m = e->mem;
+        const size_t nu = (size_t)n_utt;
+        if (e->q_next.reserve(m, S3A_GROW_DEV, nu, nu, 0, 4) != S3A_OK || e->q_nfr.reserve(m, S3A_GROW_DEV, nu, nu) != S3A_OK
+            || e->q_order.reserve(m, S3A_GROW_DEV, nu, nu) != S3A_OK || e->q_res.reserve(m, S3A_GROW_DEV, nu, nu, PSF_QRES * 4) != S3A_OK
+            || e->q_row0.reserve(m, S3A_GROW_DEV, nu, nu) != S3A_OK
+            || e->q_seg.reserve(m, S3A_GROW_DEV, nu, nu, e->q_seg_cap * sizeof(s3a_psfwd_seg_t)) != S3A_OK) return S3A_EHIP;
     }
-    if (e->feat_cap < total * D) {
-        if (e->feat_d) (void)hipFree(e->feat_d);
-        e->feat_d = NULL; e->feat_cap = 0;
-        HIPCHK(hipMalloc((void **)&e->feat_d, (total * D + 1) * 4));
-        e->feat_cap = total * D;
-    }
-    if (e->slot_cap < total + 1) {
-        if (e->slot_row_d) (void)hipFree(e->slot_row_d);
-        e->slot_row_d = NULL; e->slot_cap = 0;
-        HIPCHK(hipMalloc((void **)&e->slot_row_d, (total + 1) * 4));
-        e->slot_cap = total + 1;
-    }
-    if (e->raw_cap < (total + 1) * M.n_sen) {
-        if (e->raw_d) (void)hipFree(e->raw_d);
-        e->raw_d = NULL; e->raw_cap = 0;
-        HIPCHK(hipMalloc((void **)&e->raw_d, (total + 1) * M.n_sen * 2));
-        e->raw_cap = (total + 1) * M.n_sen;
-    }
-    if (e->q_cap < (size_t)n_utt) {
-        void *qp[] = { e->q_next_d, e->q_nfr_d, e->q_res_d, e->q_row0_d, e->q_seg_d, e->q_order_d };
-        for (void *q : qp) if (q) (void)hipFree(q);
-        e->q_next_d = e->q_nfr_d = e->q_res_d = e->q_order_d = NULL; e->q_row0_d = NULL; e->q_seg_d = NULL; e->q_cap = 0;
-        HIPCHK(hipMalloc((void **)&e->q_next_d, 4)); HIPCHK(hipMalloc((void **)&e->q_nfr_d, (size_t)n_utt * 4)); HIPCHK(hipMalloc((void **)&e->q_order_d, (size_t)n_utt * 4));
-        HIPCHK(hipMalloc((void **)&e->q_res_d, (size_t)n_utt * PSF_QRES * 4)); HIPCHK(hipMalloc((void **)&e->q_row0_d, (size_t)n_utt * 8));
-        HIPCHK(hipMalloc((void **)&e->q_seg_d, (size_t)n_utt * e->q_seg_cap * sizeof(s3a_psfwd_seg_t)));
-        e->q_cap = n_utt;
-    }
-    for (int32_t z = 0; z < n_utt; z++)
-        if (n_frames[z]) HIPCHK(hipMemcpyAsync(e->feat_d + (size_t)row0[z] * D, feat[z], (size_t)n_frames[z] * D * 4, hipMemcpyHostToDevice, e->stream));
+    if ((rc = decode_upload_feat(e, D, n_utt, feat, n_frames, row0)) != S3A_OK) return rc;
     std::vector<int32_t> rows(total + 1);
     for (size_t i = 0; i < total; i++) rows[i] = (int32_t)i;
-    HIPCHK(hipMemcpyAsync(e->slot_row_d, rows.data(), total * 4, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->q_nfr_d, n_frames, (size_t)n_utt * 4, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->q_row0_d, row0.data(), (size_t)n_utt * 8, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->slot_row.d, rows.data(), total * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->q_nfr.d, n_frames, (size_t)n_utt * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->q_row0.d, row0.data(), (size_t)n_utt * 8, hipMemcpyHostToDevice, e->stream));
     /* the lanes take the utterances longest first: whatever is taken last, when the other lanes run dry, is short (pocketsphinx_batch
      * walks the control file in order; an utterance's result does not depend on when it is decoded -- every one starts from a new
      * decoder's state -- and the results are kept by utterance index) */
     std::vector<int32_t> order(n_utt);
     for (int32_t z = 0; z < n_utt; z++) order[z] = z;
     std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return n_frames[a] > n_frames[b]; });
-    HIPCHK(hipMemcpyAsync(e->q_order_d, order.data(), (size_t)n_utt * 4, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemsetAsync(e->q_next_d, 0, 4, e->stream));
-    HIPCHK(hipMemsetAsync(e->q_res_d, 0xff, (size_t)n_utt * PSF_QRES * 4, e->stream));
+    HIPCHK(hipMemcpyAsync(e->q_order.d, order.data(), (size_t)n_utt * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemsetAsync(e->q_next.d, 0, 4, e->stream));
+    HIPCHK(hipMemsetAsync(e->q_res.d, 0xff, (size_t)n_utt * PSF_QRES * 4, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));            /* (rows is a local) */
     HIPCHK(hipEventRecord(e->ev0, e->stream));
     const int32_t n_wg = n_utt < e->n_lanes ? n_utt : e->n_lanes;
     PsfQueue Q;
-    Q.n_utt = n_utt; Q.seg_cap = e->q_seg_cap; Q.next = e->q_next_d; Q.nfr = e->q_nfr_d; Q.row0 = e->q_row0_d; Q.raw = e->raw_d;
-    Q.res = e->q_res_d; Q.seg = e->q_seg_d; Q.ready = NULL; Q.order = NULL;
-    int32_t rc;
+    Q.n_utt = n_utt; Q.seg_cap = e->q_seg_cap; Q.next = e->q_next.d; Q.nfr = e->q_nfr.d; Q.row0 = e->q_row0.d; Q.raw = e->raw.d;
+    Q.res = e->q_res.d; Q.seg = e->q_seg.d; Q.ready = NULL; Q.order = NULL;
     if (n_utt <= n_wg || !s3a_variants()->ps_overlap) {
-        rc = s3a_ps_score_slots_dev(scorer, e->feat_d, e->slot_row_d, (int32_t)total, e->raw_d, e->stream);
+        rc = s3a_ps_score_slots_dev(scorer, e->feat.d, e->slot_row.d, (int32_t)total, e->raw.d, e->stream);
         if (rc != S3A_OK) return rc;
         HIPCHK(hipEventRecord(e->ev_mid, e->stream));
     }
@@ -2028,7 +1998,7 @@ s3a_psfwd_decode_queue(s3a_psfwd_t *e, s3a_ps_mgau_t *scorer, int32_t n_utt, con
             const int32_t u1 = u0 == 0 ? n_wg : (u0 + group < n_utt ? u0 + group : n_utt);
             const long long r0 = row0[u0], r1 = u1 < n_utt ? row0[u1] : (long long)total;
             if (r1 > r0) {
-                rc = s3a_ps_score_slots_dev(scorer, e->feat_d, e->slot_row_d + r0, (int32_t)(r1 - r0), e->raw_d + (size_t)r0 * M.n_sen, e->stream_sc);
+                rc = s3a_ps_score_slots_dev(scorer, e->feat.d, e->slot_row.d + r0, (int32_t)(r1 - r0), e->raw.d + (size_t)r0 * M.n_sen, e->stream_sc);
                 if (rc != S3A_OK) { (void)hipStreamSynchronize(e->stream_sc); return rc; }
             }
             hipLaunchKernelGGL(k_psf_mark_ready, dim3(1), dim3(64), 0, e->stream_sc, e->q_ready_d, u1);
@@ -2039,7 +2009,7 @@ s3a_psfwd_decode_queue(s3a_psfwd_t *e, s3a_ps_mgau_t *scorer, int32_t n_utt, con
             u0 = u1;
         }
     }
-    if (!Q.ready) Q.order = e->q_order_d;
+    if (!Q.ready) Q.order = e->q_order.d;
     NEPL_LAUNCH(k_psf_queue, dim3(n_wg), M, e->lanes_d, Q, compallsen);
     HIPCHK(hipGetLastError());
     if (Q.ready) {                  /* the scoring stream ends before the search can, but the timed region closes on both */
@@ -2048,8 +2018,8 @@ s3a_psfwd_decode_queue(s3a_psfwd_t *e, s3a_ps_mgau_t *scorer, int32_t n_utt, con
     }
     HIPCHK(hipEventRecord(e->ev1, e->stream));
     e->q_res_h.resize((size_t)n_utt * PSF_QRES); e->q_seg_h.resize((size_t)n_utt * e->q_seg_cap);
-    HIPCHK(hipMemcpyAsync(e->q_res_h.data(), e->q_res_d, (size_t)n_utt * PSF_QRES * 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(e->q_seg_h.data(), e->q_seg_d, (size_t)n_utt * e->q_seg_cap * sizeof(s3a_psfwd_seg_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(e->q_res_h.data(), e->q_res.d, (size_t)n_utt * PSF_QRES * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(e->q_seg_h.data(), e->q_seg.d, (size_t)n_utt * e->q_seg_cap * sizeof(s3a_psfwd_seg_t), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));

@@ -38,7 +38,8 @@ struct s3a_ps_dev_s {
     int32_t *dist_id, *scr, *best;
     int16_t *out, *out_h;
     hipStream_t stream;
-    float *bdist; int32_t *bdist_id; size_t bdist_cap;     /* s3a_ps_score_slots_dev's top-N lists */
+    s3a_grow<float> bdist; s3a_grow<int32_t> bdist_id;     /* s3a_ps_score_slots_dev's top-N lists (one capacity) */
+    s3a_hostmem mem;                /* every device / pinned buffer of this structure is its */
 };
 
 __global__ void
@@ -507,14 +508,8 @@ s3a_ps_score_slots_dev(s3a_ps_mgau_t *ps, const float *feat_dev, const int32_t *
     tile = tile < PS_FT ? PS_FT : (tile / PS_FT) * PS_FT;
     if (tile > n_slots) tile = ((n_slots + PS_FT - 1) / PS_FT) * PS_FT;
     if (tile < PS_FT) tile = PS_FT;
-    if (dv->bdist_cap < (size_t)tile * per_slot) {
-        if (dv->bdist) (void)hipFree(dv->bdist);
-        if (dv->bdist_id) (void)hipFree(dv->bdist_id);
-        dv->bdist = NULL; dv->bdist_id = NULL; dv->bdist_cap = 0;
-        HIPCHK(hipMalloc((void **)&dv->bdist, (size_t)tile * per_slot * 4));
-        HIPCHK(hipMalloc((void **)&dv->bdist_id, (size_t)tile * per_slot * 4));
-        dv->bdist_cap = (size_t)tile * per_slot;
-    }
+    if (dv->bdist.reserve(dv->mem, S3A_GROW_DEV, (size_t)tile * per_slot, (size_t)tile * per_slot) != S3A_OK
+        || dv->bdist_id.reserve(dv->mem, S3A_GROW_DEV, (size_t)tile * per_slot, (size_t)tile * per_slot) != S3A_OK) return S3A_EHIP;
     LogAddShifted la = { dv->tab, dv->tab_size, dv->lm_zero };
     const int64_t items = (int64_t)M * F * P;
     if (ps->one_to_one && F == 1 && nd == 8 && ps->veclen == 39 && ps->topn <= nd && M == S && dv->meanS && !s3a_variants()->ps_score_by_gaussian) {
@@ -544,18 +539,19 @@ s3a_ps_score_slots_dev(s3a_ps_mgau_t *ps, const float *feat_dev, const int32_t *
         const int32_t n = n_slots - s0 < tile ? n_slots - s0 : tile;
         hipLaunchKernelGGL(k_ps_dist_slots, dim3((uint32_t)((items + PSB - 1) / PSB), (n + PS_FT - 1) / PS_FT), dim3(PSB),
                            (size_t)PS_FT * ps->veclen * 4 + 16, st, M, F, nd, P, ps->veclen, ps->topn, dv->featlen, dv->featoff,
-                           dv->meanT, dv->precT, dv->det, feat_dev, slot_row_dev, s0, n, dv->bdist, dv->bdist_id);
+                           dv->meanT, dv->precT, dv->det, feat_dev, slot_row_dev, s0, n, dv->bdist.d, dv->bdist_id.d);
         hipLaunchKernelGGL(k_ps_senone_slots, dim3((S + PSB - 1) / PSB, n), dim3(PSB), 0, st, S, M, F, nd, ps->topn, ps->aw,
-                           dv->mgau, dv->pdf, dv->bdist, dv->bdist_id, la, slot_row_dev, s0, raw_dev);
+                           dv->mgau, dv->pdf, dv->bdist.d, dv->bdist_id.d, la, slot_row_dev, s0, raw_dev);
     }
     HIPCHK(hipGetLastError());
     return S3A_OK;
 }
 
-#define DM(ptr, bytes) HIPCHK(hipMalloc((void **)&(ptr), (bytes) ? (bytes) : 4))
+#define DM(ptr, bytes) do { if (!dv->mem.dev(ptr, bytes)) return S3A_EHIP; } while (0)
 
-extern "C" int32_t
-s3a_ps_dev_create(s3a_ps_mgau_t *ps)
+/* (a failure leaves what was made so far to s3a_ps_dev_create, which destroys it) */
+static int32_t
+ps_dev_fill(s3a_ps_mgau_t *ps)
 {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -566,8 +562,7 @@ s3a_ps_dev_create(s3a_ps_mgau_t *ps)
     while (P < ps->n_density) P <<= 1;
     if (P > PSB) { s3a_set_error("s3a_ps_ms_mgau_init: %d densities per codebook exceed the kernel's %d", ps->n_density, PSB); return S3A_EUNSUP; }
     if (ps->veclen * 4 > 48 * 1024) { s3a_set_error("s3a_ps_ms_mgau_init: feature vector too long"); return S3A_EUNSUP; }
-    s3a_ps_dev_s *dv = new s3a_ps_dev_s();
-    memset(dv, 0, sizeof *dv);
+    s3a_ps_dev_s *dv = new s3a_ps_dev_s();     /* (value-initialised) */
     ps->dev = dv;
     dv->P = P;
     const int32_t M = ps->n_mgau, F = ps->n_feat, nd = ps->n_density, D = ps->veclen, S = ps->n_sen;
@@ -592,7 +587,7 @@ s3a_ps_dev_create(s3a_ps_mgau_t *ps)
     DM(dv->sen_active, (size_t)S); DM(dv->mgau_active, (size_t)M); DM(dv->feat, (size_t)D * 4);
     DM(dv->dist, (size_t)M * F * ps->topn * 4); DM(dv->dist_id, (size_t)M * F * ps->topn * 4);
     DM(dv->scr, (size_t)S * 4); DM(dv->best, 4); DM(dv->out, (size_t)S * 2);
-    HIPCHK(hipHostMalloc((void **)&dv->out_h, (size_t)S * 2));
+    if (!dv->mem.pin(dv->out_h, (size_t)S * 2)) return S3A_EHIP;
     HIPCHK(hipMemcpy(dv->meanT, mt.data(), nT * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dv->precT, pt.data(), nT * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dv->det, dt.data(), dt.size() * 4, hipMemcpyHostToDevice));
@@ -631,17 +626,20 @@ s3a_ps_dev_create(s3a_ps_mgau_t *ps)
     return S3A_OK;
 }
 
+extern "C" int32_t
+s3a_ps_dev_create(s3a_ps_mgau_t *ps)
+{
+    const int32_t rc = ps_dev_fill(ps);
+    if (rc != S3A_OK) s3a_ps_dev_destroy(ps);
+    return rc;
+}
+
 extern "C" void
 s3a_ps_dev_destroy(s3a_ps_mgau_t *ps)
 {
     s3a_ps_dev_s *dv = ps ? ps->dev : NULL;
     if (!dv) return;
-    void *ptrs[] = { dv->meanS, dv->precS, dv->meanT, dv->precT, dv->det, dv->featlen, dv->featoff, dv->pdf, dv->mgau, dv->tab,
-                     dv->sen_active, dv->mgau_active, dv->feat, dv->dist, dv->dist_id, dv->scr, dv->best, dv->out };
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (dv->bdist) (void)hipFree(dv->bdist);
-    if (dv->bdist_id) (void)hipFree(dv->bdist_id);
-    if (dv->out_h) (void)hipHostFree(dv->out_h);
+    dv->mem.free_all();
     if (dv->stream) (void)hipStreamDestroy(dv->stream);
     delete dv;
     ps->dev = NULL;

@@ -113,7 +113,7 @@ s3a_scorer_init(s3a_mgau_model_t *g, const int16_t *cd2cisen, int32_t n_sen, int
         s3a_set_error("32-bit log-add tables are not supported by the scoring kernels");
         return NULL;
     }
-    sc = (s3a_scorer_t *)calloc(1, sizeof *sc);
+    sc = new s3a_scorer_s();           /* (value-initialised) */
     sc->g = g;
     sc->n_sen = n_sen;
     sc->n_ci_sen = n_ci_sen;
@@ -130,15 +130,17 @@ s3a_scorer_init(s3a_mgau_model_t *g, const int16_t *cd2cisen, int32_t n_sen, int
     {
         uint8_t *nc = (uint8_t *)malloc(n_sen);
         for (s = 0; s < n_sen; s++) nc[s] = (uint8_t)g->n_comp[s];
-        if (hipMalloc(&sc->cd2cisen_d, sizeof(int16_t) * n_sen) != hipSuccess
-            || hipMalloc(&sc->ncomp_d, n_sen) != hipSuccess
-            || hipMalloc(&sc->x_d, sizeof(float) * d->D4 * 4) != hipSuccess
-            || hipMalloc(&sc->act_d, n_sen) != hipSuccess
-            || hipMalloc(&sc->scr_d, sizeof(int32_t) * n_sen) != hipSuccess
-            || hipMalloc(&sc->ci_d, sizeof(int32_t) * (n_ci_sen > 0 ? n_ci_sen : 1)) != hipSuccess
-            || hipMalloc(&sc->misc_d, sizeof(int32_t) * 8) != hipSuccess
-            || hipMalloc(&sc->gpart_d, sizeof(int32_t) * 3 * (sc->gp_n = ((n_sen - n_ci_sen) * d->CP + 255) / 256, sc->gp_n > 0 ? sc->gp_n : 1)) != hipSuccess
-            || hipHostMalloc(&sc->misc_h, sizeof(int32_t) * 8) != hipSuccess
+        s3a_hostmem &m = sc->mem;
+        sc->gp_n = ((n_sen - n_ci_sen) * d->CP + 255) / 256;
+        if (!m.dev(sc->cd2cisen_d, sizeof(int16_t) * n_sen)
+            || !m.dev(sc->ncomp_d, n_sen)
+            || !m.dev(sc->x_d, sizeof(float) * d->D4 * 4)
+            || !m.dev(sc->act_d, n_sen)
+            || !m.dev(sc->scr_d, sizeof(int32_t) * n_sen)
+            || !m.dev(sc->ci_d, sizeof(int32_t) * (n_ci_sen > 0 ? n_ci_sen : 1))
+            || !m.dev(sc->misc_d, sizeof(int32_t) * 8)
+            || !m.dev(sc->gpart_d, sizeof(int32_t) * 3 * (sc->gp_n > 0 ? sc->gp_n : 1))
+            || !m.pin(sc->misc_h, sizeof(int32_t) * 8)
             || hipMemcpy(sc->cd2cisen_d, cd2cisen, sizeof(int16_t) * n_sen, hipMemcpyHostToDevice) != hipSuccess
             || hipMemcpy(sc->ncomp_d, nc, n_sen, hipMemcpyHostToDevice) != hipSuccess
             || hipMemset(sc->x_d, 0, sizeof(float) * d->D4 * 4) != hipSuccess
@@ -164,12 +166,9 @@ s3a_scorer_init_private(s3a_mgau_model_t *g, const int16_t *cd2cisen, int32_t n_
 {
     s3a_scorer_t *sc = s3a_scorer_init(g, cd2cisen, n_sen, n_ci_sen, ds_ratio, cond_ds, ci_pbeam, tighten_factor, max_cd);
     if (!sc) return NULL;
-    sc->bstidx_d = sc->bstscr_d = sc->updatetime_d = NULL;
-    if (hipMalloc(&sc->bstidx_d, sizeof(int32_t) * n_sen) != hipSuccess
-        || hipMalloc(&sc->bstscr_d, sizeof(int32_t) * n_sen) != hipSuccess
-        || hipMalloc(&sc->updatetime_d, sizeof(int32_t) * n_sen) != hipSuccess) {
+    if (!sc->mem.dev(sc->bstidx_d, sizeof(int32_t) * n_sen) || !sc->mem.dev(sc->bstscr_d, sizeof(int32_t) * n_sen)
+        || !sc->mem.dev(sc->updatetime_d, sizeof(int32_t) * n_sen)) {
         s3a_set_error("s3a_scorer_init_private: device allocation failed");
-        sc->own_state = 1;
         s3a_scorer_free(sc);
         return NULL;
     }
@@ -182,13 +181,9 @@ extern "C" void
 s3a_scorer_free(s3a_scorer_t *sc)
 {
     if (!sc) return;
-    (void)hipFree(sc->cd2cisen_d); (void)hipFree(sc->ncomp_d); (void)hipFree(sc->x_d);
-    (void)hipFree(sc->act_d); (void)hipFree(sc->scr_d); (void)hipFree(sc->ci_d);
-    (void)hipFree(sc->misc_d); (void)hipFree(sc->gpart_d);
-    if (sc->own_state) { (void)hipFree(sc->bstidx_d); (void)hipFree(sc->bstscr_d); (void)hipFree(sc->updatetime_d); }
-    if (sc->misc_h) (void)hipHostFree(sc->misc_h);
+    sc->mem.free_all();
     free(sc->cd2cisen_h); free(sc->ci_occ_h); free(sc->idx_h);
-    free(sc);
+    delete sc;
 }
 
 extern "C" int32_t
@@ -381,13 +376,11 @@ s3a_comsen_init(int32_t n_comstate, const int32_t *comstate_off, const int16_t *
             s3a_set_error("s3a_comsen_init: composite state %d has no member senone", i);
             return NULL;
         }
-    cs = (s3a_comsen_t *)calloc(1, sizeof *cs);
+    cs = new s3a_comsen_s();           /* (value-initialised) */
     cs->n_comstate = n_comstate;
     cs->n_list = n_list;
-    if (hipMalloc(&cs->off_d, 4 * (n_comstate + 1)) != hipSuccess
-        || hipMalloc(&cs->wt_d, 4 * n_comstate) != hipSuccess
-        || hipMalloc(&cs->out_d, 4 * n_comstate) != hipSuccess
-        || hipMalloc(&cs->list_d, 2 * n_list) != hipSuccess
+    if (!cs->mem.dev(cs->off_d, 4 * (n_comstate + 1)) || !cs->mem.dev(cs->wt_d, 4 * n_comstate)
+        || !cs->mem.dev(cs->out_d, 4 * n_comstate) || !cs->mem.dev(cs->list_d, 2 * n_list)
         || hipMemcpy(cs->off_d, comstate_off, 4 * (n_comstate + 1), hipMemcpyHostToDevice) != hipSuccess
         || hipMemcpy(cs->wt_d, comwt, 4 * n_comstate, hipMemcpyHostToDevice) != hipSuccess
         || hipMemcpy(cs->list_d, comstate, 2 * n_list, hipMemcpyHostToDevice) != hipSuccess
@@ -403,23 +396,21 @@ extern "C" void
 s3a_comsen_free(s3a_comsen_t *cs)
 {
     if (!cs) return;
-    (void)hipFree(cs->off_d); (void)hipFree(cs->wt_d); (void)hipFree(cs->out_d);
-    (void)hipFree(cs->list_d); (void)hipFree(cs->scr_d);
+    cs->mem.free_all();
     if (cs->stream) (void)hipStreamDestroy(cs->stream);
-    free(cs);
+    delete cs;
 }
 
 extern "C" int32_t
 s3a_dict2pid_comsenscr(s3a_comsen_t *cs, const int32_t *senscr, int32_t n_sen, int32_t *comsenscr)
 {
-    int32_t rc;
     if (!cs || !senscr || !comsenscr || n_sen <= 0)
         return S3A_EINVAL;
-    if ((rc = s3a_dev_grow((void **)&cs->scr_d, &cs->scr_cap, (size_t)n_sen * 4)) != S3A_OK)
-        return rc;
-    HIPCHK(hipMemcpyAsync(cs->scr_d, senscr, (size_t)n_sen * 4, hipMemcpyHostToDevice, cs->stream));
+    if (cs->scr.reserve(cs->mem, S3A_GROW_DEV, (size_t)n_sen, (size_t)n_sen) != S3A_OK)
+        return S3A_EHIP;
+    HIPCHK(hipMemcpyAsync(cs->scr.d, senscr, (size_t)n_sen * 4, hipMemcpyHostToDevice, cs->stream));
     hipLaunchKernelGGL(k_comsenscr, dim3((cs->n_comstate + 255) / 256), dim3(256), 0, cs->stream,
-                       cs->n_comstate, cs->off_d, cs->list_d, cs->wt_d, cs->scr_d, cs->out_d);
+                       cs->n_comstate, cs->off_d, cs->list_d, cs->wt_d, cs->scr.d, cs->out_d);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(comsenscr, cs->out_d, (size_t)cs->n_comstate * 4, hipMemcpyDeviceToHost, cs->stream));
     HIPCHK(hipStreamSynchronize(cs->stream));

@@ -31,6 +31,7 @@ struct s3a_scorer_s {
     int32_t *bstidx_d, *bstscr_d, *updatetime_d;
     int own_state;
     int32_t *ci_occ_h, *idx_h;
+    s3a_hostmem mem;        /* the device / pinned buffers made HERE are its: the model's state arrays, when borrowed, are not */
 };
 
 
@@ -61,14 +62,17 @@ struct s3a_scorer_s {
 
 struct s3a_comsen_s {
     int32_t n_comstate, n_list;
-    int32_t *off_d, *wt_d, *out_d, *scr_d;
+    int32_t *off_d, *wt_d, *out_d;
     int16_t *list_d;
-    size_t scr_cap;
+    s3a_grow<int32_t> scr;
     hipStream_t stream;
+    s3a_hostmem mem;
 };
 
 
-struct s3a_lexsearch_s {
+/* the lextrees themselves: host tables and the static device arrays.  A clone (s3a_lexsearch_clone) copies this half from its
+ * prototype, device pointers included -- it borrows those arrays, its own owner never hears of them */
+struct s3a_lextrees_s {
     int32_t n_tree, N;                  /* N = total nodes */
     int32_t n_emit, n_tmat, n_sen, n_comsen, n_lcmax;
     std::vector<int32_t> node_base;     /* [n_tree+1] */
@@ -87,6 +91,14 @@ struct s3a_lexsearch_s {
     int32_t *d_tp;
     int16_t *d_sseq, *d_comsseq, *d_comstate;
     int32_t *d_comstate_off;
+    int32_t *d_tree_of;                 /* [N] tree index of every node */
+    int32_t *d_rootnodes, n_rootnodes;  /* the distinct root nodes of all trees */
+    int32_t *d_ps, *d_psof_off, *d_psof, *d_psmem_off, *d_psmem, n_pset;    /* parent-set ids: of a node, of a node's children */
+    int32_t ent_cap;                    /* entries of the enter scratch: every root list entered once */
+    int32_t pack_max_exits;
+};
+
+struct s3a_lexsearch_s : s3a_lextrees_s {
     /* state (device) */
     int32_t *d_sc, *d_hist;             /* [3][N] */
     int32_t *d_outs, *d_outh, *d_bests, *d_frame;
@@ -105,27 +117,23 @@ struct s3a_lexsearch_s {
     int32_t *d_nexit;                   /* [n_tree] + [n_tree] error flags */
     int32_t *d_calls, *d_ent, *d_eflag, *d_first;   /* enter scratch */
     unsigned long long *d_key;
-    int32_t ent_cap;
     int32_t *d_thr;                     /* [8] thresholds + frame statistics */
-    int32_t *d_tree_of;                 /* [N] tree index of every node */
     int32_t *d_done;                    /* workgroup completion counter of the fused finishing kernel */
     int32_t *d_hbin;                    /* [1000] lextree_hmm_histbin bins | [1000] = the histogram beam */
-    int32_t *d_rootnodes, n_rootnodes;  /* the distinct root nodes of all trees */
-    int32_t *d_ps, *d_psof_off, *d_psof, *d_psmem_off, *d_psmem, *d_pstamp, n_pset;    /* parent-set ids: of a node, of a node's children; frame stamps */
+    int32_t *d_pstamp;                  /* [n_pset] frame stamps of the parent sets */
     int32_t *d_ctot, *d_n0;             /* per-call root counts [4096], list lengths before the entries [n_tree] */
     int32_t hist_bound, last_nnxt;      /* host upper bound on the coming frame's active HMMs */
     int32_t row_bound;                  /* ... on its LONGEST active list (per tree: sizes the per-position grids) */
     std::vector<int32_t> nnxt_t;        /* per tree: what the last search emitted */
     int32_t *d_pack, *h_pack;           /* per-frame result record (device / pinned host) */
-    int32_t pack_max_exits;
     int32_t *h_ring;                    /* pinned staging ring for enter calls */
     int32_t ring_slot;
     int32_t *h_pin;                     /* pinned host mirror for small read-backs */
     hipStream_t stream;
     int own_stream;
     int opt_calls_by_copy, opt_scan_chained;    /* S3A_CALLS_BY_COPY / S3A_SCAN_CHAINED as read when the object was made (tests) */
-    int is_clone;                       /* static device arrays borrowed from a prototype (s3a_lexsearch_clone) */
     hipEvent_t ev_pack;                 /* recorded after the frame record's copy (the emission kernel follows it) */
+    s3a_hostmem mem;                    /* the device / pinned buffers THIS object made: a prototype's both halves, a clone's state */
 };
 
 

@@ -44,7 +44,6 @@
 #include "s3a_wordlevel.h"
 #include "s3a_lm3g.h"
 #include "s3a_dag.h"
-#define S3A_HOSTMEM_WHO "s3a_utt"
 #include "s3a_hostmem.h"
 
 /* A pointer that came out of a structure in memory is a GENERIC pointer to the compiler; what it makes of an access through one is
@@ -3517,9 +3516,6 @@ s3a_uttdec_free(s3a_uttdec_t *ud)
     (void)hipSetDevice(ud->device);
     (void)hipStreamSynchronize(ud->stream);
     for (auto &hl : ud->lane) {
-        if (hl.ls && ud->S.nact_all && hl.ls->d_nact[0] >= ud->S.nact_all
-            && hl.ls->d_nact[0] < ud->S.nact_all + (size_t)ud->n_lanes * 2 * WL_MAXT)
-            hl.ls->d_nact[0] = hl.ls->d_nact[1] = NULL;     /* borrowed from nact_all */
         if (hl.sc) s3a_scorer_free(hl.sc);
         if (hl.ls) s3a_lexsearch_free(hl.ls);
     }
@@ -3833,8 +3829,9 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
         ULane &u = hl.d;
         u.sc = ls->d_sc; u.hist = ls->d_hist; u.outs = ls->d_outs; u.outh = ls->d_outh; u.bests = ls->d_bests;
         u.frame = ls->d_frame; u.pos = ls->d_pos; u.posf = ls->d_posf; u.act[0] = ls->d_act[0]; u.act[1] = ls->d_act[1];
-        /* the clone's list lengths move into the engine's array (borrowed: s3a_uttdec_free takes them back) */
-        ud->mem.release(ls->d_nact[0]); ud->mem.release(ls->d_nact[1]);
+        /* the clone's list lengths move into the engine's array: the clone's owner gives its own arrays back now, and never hears of
+         * the engine's (borrowed) */
+        ls->mem.release(ls->d_nact[0]); ls->mem.release(ls->d_nact[1]);
         ls->d_nact[0] = ud->S.nact_all + ((size_t)z * 2) * WL_MAXT; ls->d_nact[1] = ud->S.nact_all + ((size_t)z * 2 + 1) * WL_MAXT;
         u.nact[0] = ls->d_nact[0]; u.nact[1] = ls->d_nact[1]; u.turn = ls->d_turn; u.selfemit = ls->d_selfemit;
         u.cnt = ls->d_cnt; u.base = ls->d_cand; u.best = ls->d_best; u.exits = ls->d_exit; u.nexit = ls->d_nexit;

@@ -2,13 +2,15 @@
  * tests/hostmem_check.cc -- TEST INFRASTRUCTURE: cmusphinx_amd/csrc/s3a_hostmem.h on the CPU (tests/test_hostmem.py builds this with the
  * address and undefined-behaviour sanitizers and runs it).  The four allocation functions are malloc-backed stand-ins that count,
  * remember what is live and fail at the k-th allocation; one scripted life of an owner and its growing buffers runs with no failure
- * and with a failure at every allocation of the script in turn.
+ * and with a failure at every allocation of the script in turn.  The life includes a function's stack-local owner left with live
+ * buffers on every return path, a buffer taken out of it for the caller (forget), and pinned memory asked for with flags.
  */
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <map>
+#include <type_traits>
 #include "cmusphinx_amd.h"      /* S3A_OK, S3A_ENOMEM */
 
 typedef int hipError_t;
@@ -17,6 +19,7 @@ static const hipError_t hipSuccess = 0, hipErrorOutOfMemory = 2;
 static std::map<void *, int> g_live;    /* pointer -> 1 device, 2 pinned */
 static int g_allocs, g_fail_at, g_bad;
 static size_t g_last_bytes;
+static unsigned g_last_flags;
 static char g_err[256];
 
 #define CHECK(c) do { if (!(c)) { fprintf(stderr, "hostmem_check: %s:%d: fail_at %d: %s\n", __FILE__, __LINE__, g_fail_at, #c); g_bad++; } } while (0)
@@ -45,7 +48,7 @@ fake_free(void *p, int kind)
     return hipSuccess;
 }
 static hipError_t hipMalloc(void **p, size_t n) { return fake_alloc(p, n, 1); }
-static hipError_t hipHostMalloc(void **p, size_t n) { return fake_alloc(p, n, 2); }
+static hipError_t hipHostMalloc(void **p, size_t n, unsigned flags = 0) { g_last_flags = flags; return fake_alloc(p, n, 2); }
 static hipError_t hipFree(void *p) { return fake_free(p, 1); }
 static hipError_t hipHostFree(void *p) { return fake_free(p, 2); }
 static void
@@ -58,6 +61,24 @@ s3a_set_error(const char *fmt, ...)
 }
 
 #include "s3a_hostmem.h"
+
+/* a function with temporaries of its own: three requests, the second handed to the caller (*out, the caller's to free with hipFree),
+ * the others freed by the local owner's scope exit on whichever path it returns */
+static bool
+temporaries(int32_t **out)
+{
+    s3a_hostmem tmp;
+    int32_t *a = NULL, *keep = NULL;
+    float *h = NULL;
+    *out = NULL;
+    if (!tmp.dev(a, 24) || !tmp.dev(keep, 40)) return false;
+    if (!tmp.pin(h, 8, 0x40000000u)) { CHECK(h == NULL); return false; }
+    CHECK(g_last_flags == 0x40000000u && g_live[h] == 2 && tmp.recs.size() == 3);
+    CHECK(tmp.forget(keep) == false && tmp.recs.size() == 2);       /* (device memory; now nobody's record) */
+    CHECK(tmp.forget(keep) == false && tmp.recs.size() == 2);       /* (unknown pointer: nothing) */
+    *out = keep;
+    return true;
+}
 
 /* one life; returns the allocation calls it made */
 static int
@@ -86,6 +107,18 @@ script(int fail_at)
         m.release(foreign);
         CHECK(foreign == NULL && g_live.size() == 3);
     }
+    /* a function's local owner: whatever it returns, only what it handed out is still live */
+    {
+        int32_t *got = NULL;
+        const size_t live0 = g_live.size();
+        before = g_allocs;
+        if (temporaries(&got)) {
+            CHECK(got && g_allocs == before + 3 && g_live.size() == live0 + 1 && g_live[got] == 1);
+            (void)hipFree(got);
+        }
+        else CHECK(got == NULL && g_allocs == fail_at);
+        CHECK(g_live.size() == live0);
+    }
     /* a pair that grows twice, with a reserve that fits in between; a failed reserve leaves it empty and the script goes on */
     for (int round = 0; round < 2; round++) {
         const size_t need = round == 0 ? 10 : 200, grow = need + need / 4 + 64;
@@ -113,8 +146,24 @@ script(int fail_at)
         else CHECK(dev.d && !dev.h && g_live[dev.d] == 1 && g_last_bytes == 800);
         dev.clear(m);
         CHECK(!dev.d && dev.cap == 0);
+        /* a pinned side with flags of its own */
+        const int32_t rc3 = dev.reserve(m, S3A_GROW_PIN, 2, 2, 4, 0, 0x40000000u);
+        if (rc3 != S3A_OK) CHECK(rc3 == S3A_ENOMEM && !dev.h && dev.cap == 0);
+        else CHECK(dev.h && g_live[dev.h] == 2 && g_last_flags == 0x40000000u && g_last_bytes == 8);
     }
 done:
+    /* scope exit of an owner with live buffers: the destructor is free_all().  (An owner cannot be copied: it would free twice.) */
+    static_assert(!std::is_copy_constructible<s3a_hostmem>::value && !std::is_copy_assignable<s3a_hostmem>::value, "s3a_hostmem must not be copyable");
+    {
+        s3a_hostmem scoped;
+        int32_t *x = NULL;
+        void *y = NULL;
+        const size_t live0 = g_live.size();
+        if (scoped.dev(x, 12) && scoped.pin(y, 12)) CHECK(g_live.size() == live0 + 2);
+        else CHECK(g_allocs == fail_at);
+        if (g_live.size() == live0) CHECK(scoped.recs.empty());
+    }
+    CHECK(g_live.size() == m.recs.size());      /* (the scoped owner freed its own, and only its own) */
     m.free_all();
     CHECK(m.recs.empty());
     CHECK(g_live.empty());              /* (nothing leaks, whatever failed) */
@@ -127,7 +176,7 @@ int
 main(void)
 {
     const int n = script(0);
-    if (n != 11) { fprintf(stderr, "hostmem_check: the script made %d allocations, 11 expected\n", n); return 1; }
+    if (n != 17) { fprintf(stderr, "hostmem_check: the script made %d allocations, 17 expected\n", n); return 1; }
     for (int k = 1; k <= n; k++) (void)script(k);
     if (g_bad) { fprintf(stderr, "hostmem_check: %d checks failed\n", g_bad); return 1; }
     printf("hostmem_check: ok (%d allocations, a failure at each in turn)\n", n);

@@ -1,8 +1,9 @@
 """cmusphinx_amd/csrc/s3a_hostmem.h without a GPU: tests/hostmem_check.cc -- the owner of an engine's allocations and its growing
 buffers over counting stand-ins for the four HIP allocation functions, one scripted life with no failure and with a failure at every
 allocation in turn -- built with the address and undefined-behaviour sanitizers and run as a program of its own.  It exits 0 only when
-every life ends with nothing live and nothing freed twice, a failed reserve leaves its buffer empty (S3A_ENOMEM) and a reserve that
-fits keeps its pointers."""
+every life ends with nothing live and nothing freed twice, a failed reserve leaves its buffer empty (S3A_ENOMEM), a reserve that
+fits keeps its pointers, an owner that goes out of scope frees what it still holds, a buffer taken out of its owner (forget) stays
+live for the caller, and hipHostMalloc's flags arrive."""
 import os
 import subprocess
 
