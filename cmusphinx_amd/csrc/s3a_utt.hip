@@ -602,8 +602,10 @@ struct UwGroup {
     int32_t nv, pad;        /* valid frames of the group (0: lane finished / idle) */
 };
 
+/* (NT == 256: at most 256 VGPRs, a wave per SIMD beside the two of a ku_frames workgroup -- the COMPANION shape <.., true, 256>,
+ * uw_geometry_companion; the 512-thread shapes have that budget by their size) */
 template <int CP, bool EXACT, bool TAB_LDS, int NT>
-__global__ void __launch_bounds__(NT)
+__global__ void __launch_bounds__(NT, NT == 256 ? 2 : 1)
 ku_score_window(const ULane *__restrict__ lanes, UShared S, int32_t n_lanes, int32_t f0, int32_t K, int32_t fpc,
                 int32_t n_chunks, int32_t n_tiles, const UwGroup *__restrict__ gdesc, int32_t n_g)
 {
@@ -1622,6 +1624,9 @@ ku_hyp(const ULane *__restrict__ lanes, WLm lm, WDict dict, UHypPar P, int32_t *
 static_assert(KF_NT == 512, "ku_frames: the word level's workgroup is the frame's workgroup");
 enum { KF_WINDOW, KF_STATIC, KF_QUEUE };
 #define KF_ST_WORDS 8
+#ifndef KF_OVERLAP_DEFAULT
+#define KF_OVERLAP_DEFAULT 1    /* scoring beside the search without being asked (kf_decode_queue; profiles/r7_overlap_experiments.txt) */
+#endif
 #define KF_STAGES 2             /* launches a call's relay may have behind its first */
 
 union KfPool {                  /* phases that never overlap share this LDS */
@@ -1692,6 +1697,15 @@ struct KfJob {
     UHypPar P;
     UBegin B;
     int32_t n_word;
+    /* SCORING BESIDE THE SEARCH (KF_QUEUE, kf_decode_queue): the call's first launches run while the later utterances are still being scored */
+    int32_t ov;                 /* 1: the call's first launch (lanes 0 .. n1 - 1); 2: the launch behind the scoring: lanes n1 .. start, and a lane below
+                                 * n1 that LEFT the first launch goes on (the workgroup of one that did not ends at once) */
+    int32_t n1;
+    const int32_t *q_ready;     /* [1] takes whose utterances are scored (NULL: all): a lane takes ticket k only if k < *q_ready, else it LEAVES */
+    int32_t *lane_left;         /* [n_lanes] 0: the lane is in the first launch's hands; 1: it left for want of scores (its LAST store of that launch);
+                                 * 2: the second launch's workgroup came, found it at work and went -- one compare-and-swap each, so exactly one
+                                 * of the two launches has the lane at any time, and a lane that finds 2 knows that everything is scored */
+    int32_t *n_resumed;         /* [1] lanes the second launch took up again */
 };
 
 /* all workgroups of the lane's cluster have finished the phase and see what the others wrote.
@@ -2916,6 +2930,17 @@ ku_frames(const ULane *__restrict__ lanes, const KfArgs *__restrict__ A, int32_t
     if (C == 1) { z = blockIdx.x; r = 0; }
     else { const int32_t b = blockIdx.x, xcd = b & 7, j = b >> 3; z = (j / C) * 8 + xcd; r = j % C; }
     if (z >= n_lanes) return;
+    if (J.ov == 2 && z < J.n1) {        /* (the first launch's lane: only one that LEFT goes on here -- what it left is acquired with its flag) */
+        if (threadIdx.x == 0) {
+            const int32_t was = atomicCAS(&J.lane_left[z], 0, 2);
+            sh.u2 = was;
+            if (was == 1) atomicAdd(J.n_resumed, 1);
+        }
+        __syncthreads();
+        if (sh.u2 != 1) return;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        __syncthreads();
+    }
     if (J.resume) {             /* (the relay: slot z of this launch continues the lane the previous launch listed there) */
         if (z >= __hip_atomic_load(&J.st_cur[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
         z = J.st_cur[KF_ST_WORDS + z];
@@ -2943,12 +2968,12 @@ ku_frames(const ULane *__restrict__ lanes, const KfArgs *__restrict__ A, int32_t
         B.local = local_ok && __popc(sh.u) == 1;
         __syncthreads();
     }
-    const long long t_launch = (long long)wall_clock64();
+    long long t_launch = (long long)wall_clock64();
     /* (ONE call site of the frame for the three modes: the frame's code is ~150 KB, and a copy per mode was three times that in a
      * kernel whose instruction cache holds 64 KB) */
     const int32_t mode = J.mode;
     const int32_t gtid = r * KF_NT + tid, gstride = C * KF_NT;
-    bool resumed = J.resume != 0, handed = false;
+    bool resumed = J.resume != 0, handed = false, all_scored = false;
     if (resumed && C > 1) {     /* (the lane's mask of a frame: clean between frames -- unless an utterance once stopped inside one) */
         if (r == 0) for (int32_t i = tid; i < KF_SENBITS / 32; i += KF_NT) L.senbits[i] = 0u;
         kf_barrier(B);
@@ -2965,7 +2990,18 @@ ku_frames(const ULane *__restrict__ lanes, const KfArgs *__restrict__ A, int32_t
         else if (mode == KF_QUEUE) {
             /* the queue's next utterance: taken by the lane's first workgroup */
             if (r == 0 && tid == 0) {
-                const int32_t u_ = atomicAdd(J.next, 1);
+                int32_t u_;
+                if (J.q_ready) {
+                    /* ticket k only if k < *q_ready: compare-and-swap, so that a refused lane holds no ticket (-1: refused -- the lane leaves,
+                     * nothing here waits for the scoring; the loop turns only when another lane took the ticket in between) */
+                    const int32_t ready = all_scored ? J.n_utt : __hip_atomic_load(J.q_ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    u_ = __hip_atomic_load(J.next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    for (;;) {
+                        if (u_ >= ready) { if (u_ < J.n_utt) u_ = -1; break; }
+                        if (__hip_atomic_compare_exchange_strong(J.next, &u_, u_ + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+                    }
+                }
+                else u_ = atomicAdd(J.next, 1);
                 sh.u = u_;
                 if (C > 1) __hip_atomic_store(&J.lane_u[z], u_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
@@ -2973,7 +3009,33 @@ ku_frames(const ULane *__restrict__ lanes, const KfArgs *__restrict__ A, int32_t
             if (r > 0 && tid == 0) sh.u = __hip_atomic_load(&J.lane_u[z], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __syncthreads();
             u = sh.u;
+            if (u < 0) {
+                /* the next take is not scored yet: the lane LEAVES (one workgroup per lane here).  It stands between two utterances; its
+                 * clocks go to memory, and its last store says that it left -- unless the second launch's workgroup has come and gone
+                 * (it found the lane at work): then everything is scored, and the lane goes on taking */
+                if (tid == 0) { sh.kacc[12] += (long long)wall_clock64() - t_launch; sh.kacc[14]++; }
+                __syncthreads();
+                if (tid < 16) { ctx->kacc[tid] += sh.kacc[tid]; sh.kacc[tid] = 0; }
+                if (tid == 0 && J.ov == 1) {
+                    ctx->kdbg[0] = t_launch; ctx->kdbg[1] = (long long)wall_clock64();
+                    ctx->kdbg[2] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4); ctx->kdbg[3] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 20);
+                }
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+                if (tid == 0) {
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                    sh.u2 = atomicCAS(&J.lane_left[z], 0, 1);
+                }
+                __syncthreads();
+                if (sh.u2 == 0) return;
+                all_scored = true;
+                t_launch = (long long)wall_clock64();
+                continue;
+            }
             if (u >= J.n_utt || sh.dead) break;
+            /* (the rows of a take beyond the launch's first ones were written while this launch ran, by kernels that ended before
+             * *q_ready said so: what was read acquires them) */
+            if (J.q_ready) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             u = J.order[J.u0 + u];              /* (the take's utterance: its index in the queue) */
             if (r == 0 && tid == 0 && J.lane_uq) J.lane_uq[z] = u;
             /* srch_utt_begin (srch.c:453-479): every per-utterance state reset, the utterance's context */
@@ -3032,13 +3094,14 @@ ku_frames(const ULane *__restrict__ lanes, const KfArgs *__restrict__ A, int32_t
         kf_barrier(B);
     }
     /* (the relay: a lane that is through counts itself out; the one that leaves `stop_at` lanes at work raises the flag for them) */
+    /* (a lane that LEFT for want of scores has returned above: still at work for the relay's count, the second launch takes it up) */
     if (J.stop_at > 0 && !handed && r == 0 && tid == 0) {
         const int32_t left = atomicSub(&J.st_cur[0], 1) - 1;
         if (left <= J.stop_at && left > 0) __hip_atomic_store(&J.st_cur[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (r == 0 && tid == 0) { sh.kacc[12] += (long long)wall_clock64() - t_launch; sh.kacc[14]++; }
     if (r == 0 && tid < 16) ctx->kacc[tid] += sh.kacc[tid];             /* (KF_QUEUE: the lane's last utterance has its frames' share already) */
-    if (r == 0 && tid == 0 && J.mode == KF_WINDOW && J.fg0 == 512) {
+    if (r == 0 && tid == 0 && ((J.mode == KF_WINDOW && J.fg0 == 512) || J.ov == 1 || (J.ov == 2 && z >= J.n1))) {
         ctx->kdbg[0] = t_launch; ctx->kdbg[1] = (long long)wall_clock64();
         ctx->kdbg[2] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4); ctx->kdbg[3] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 20);
     }
@@ -3429,6 +3492,13 @@ struct s3a_uttdec_s {
     std::vector<hipEvent_t> kf_evs;
     int32_t kf_ev_n, kf_n_score, kf_n_frames;
     double kf_score_ms, kf_frames_ms;
+    /* scoring beside the search (kf_decode_queue): the second stream and the events that order the two, the lanes' flags, the last call's figures */
+    hipStream_t kf_stream2;
+    hipEvent_t kf_ov_ev[2];     /* the first utterances scored | the second stream's launch through */
+    int32_t *d_kfleft;          /* [n_lanes] a lane left for want of scores */
+    int32_t kf_overlapped;      /* the last call ran that plan */
+    int32_t kf_n_resumed;       /* ... lanes that left and were resumed */
+    int32_t kf_comp_lds;        /* dynamic LDS a companion scoring workgroup may take beside one ku_frames workgroup (0: not asked yet) */
 };
 
 /* engines with ku_frames alive per device: an engine that is alone on its device may give a lane a cluster of workgroups */
@@ -3522,6 +3592,8 @@ s3a_uttdec_free(s3a_uttdec_t *ud)
     if (ud->kf_counted) { g_kf_live[ud->device]--; ud->kf_counted = 0; kf_device_unlock(ud->device); }
     for (auto e : ud->kf_evs) (void)hipEventDestroy(e);
     ud->kf_evs.clear();
+    for (auto &e : ud->kf_ov_ev) if (e) { (void)hipEventDestroy(e); e = NULL; }
+    if (ud->kf_stream2) { (void)hipStreamSynchronize(ud->kf_stream2); (void)hipStreamDestroy(ud->kf_stream2); ud->kf_stream2 = NULL; }
     if (ud->dag) s3a_dagpass_free(ud->dag);
     for (auto &fg_ : ud->graphs) if (fg_.exec) (void)hipGraphExecDestroy(fg_.exec);
     if (ud->ev0) (void)hipEventDestroy(ud->ev0);
@@ -3801,6 +3873,7 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
         DM(ud->mem, ud->d_kfbar, (size_t)n_lanes * 8);
         if (hipMemset(ud->d_kfbar, 0, (size_t)n_lanes * 8) != hipSuccess) goto fail;
         DM(ud->mem, ud->d_kfrelay, ((size_t)(KF_STAGES + 1) * (KF_ST_WORDS + n_lanes) + (size_t)3 * n_lanes) * 4);
+        DM(ud->mem, ud->d_kfleft, (size_t)n_lanes * 4);
         if (ud->device >= 0 && ud->device < 64) { g_kf_live[ud->device]++; ud->kf_counted = 1; ud->kf_shared = kf_device_lock(ud->device) ? 0 : 1; }
     }
     ud->scan_small_from = O.scan_small_from > 0 ? O.scan_small_from : 64;
@@ -4010,6 +4083,53 @@ uw_geometry(const s3a_uttdec_t *ud, int32_t n_lanes, int32_t total_slots = 0)
     return q;
 }
 
+/* THE COMPANION SHAPE: a scoring workgroup that fits a CU BESIDE one ku_frames workgroup (kf_decode_queue scores the later utterances
+ * of a queue while the first ones are searched).  256 threads at no more than 256 VGPRs are one wave per SIMD beside the search's two of
+ * 128; the LDS is what the CU has left beside the search's workgroup, by the kernels' own figures (ku_frames' static LDS rounded up to the
+ * allocation granule, 1 280 B on a 160 KB CU -- and to 512 B, the older parts', whichever leaves less): the log-add table, the
+ * transposition tile and as many frames per chunk as still fit (at most 88).  Same body, same rows as every other shape. */
+#define UW_COMP_FPC_MAX 88
+template <int NE, bool EXACT>
+static int32_t
+kf_static_lds(void)
+{
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, (const void *)ku_frames<NE, EXACT>) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    return (int32_t)fa.sharedSizeBytes;
+}
+static int32_t
+uw_companion_lds(s3a_uttdec_t *ud)
+{
+    if (ud->kf_comp_lds == 0) {
+        const int32_t cu_lds = 160 * 1024;
+        int32_t lane = ud->S.ne == 5 ? (ud->exact ? kf_static_lds<5, true>() : kf_static_lds<5, false>())
+                                     : (ud->exact ? kf_static_lds<3, true>() : kf_static_lds<3, false>());
+        if (lane <= 0 || lane > cu_lds / 2) lane = cu_lds / 2;
+        const int32_t left = cu_lds - max((lane + 1279) / 1280 * 1280, (lane + 511) / 512 * 512);
+        ud->kf_comp_lds = left / 1280 * 1280;
+    }
+    return ud->kf_comp_lds;
+}
+static UwGeom
+uw_geometry_companion(s3a_uttdec_t *ud, int32_t total_slots)
+{
+    const UShared &S = ud->S;
+    const int32_t room = uw_companion_lds(ud);
+    UwGeom q;
+    q.nt = 256; q.tab_lds = 1;
+    q.n_tiles = S.Gpad / q.nt;
+    q.fpc = min(UW_COMP_FPC_MAX, ((total_slots + UW_FB - 1) / UW_FB) * UW_FB);
+    while (q.fpc > UW_FB && uw_lds_bytes(q.fpc, q.nt, true, S.tab_size) > (size_t)room) q.fpc -= UW_FB;
+    if (uw_lds_bytes(q.fpc, q.nt, true, S.tab_size) > (size_t)room) {       /* (a table that does not fit beside the search stays in memory) */
+        q.tab_lds = 0;
+        q.fpc = min(UW_COMP_FPC_MAX, ((total_slots + UW_FB - 1) / UW_FB) * UW_FB);
+    }
+    q.n_chunks = (total_slots + q.fpc - 1) / q.fpc;
+    q.grid = ((q.n_tiles + 7) / 8) * q.n_chunks * 8;
+    q.lds = uw_lds_bytes(q.fpc, q.nt, q.tab_lds != 0, S.tab_size);
+    return q;
+}
+
 template <int CP, bool EXACT>
 static hipError_t
 uw_launch_cp(const s3a_uttdec_t *ud, const UwGeom &q, int32_t n, int32_t f0, hipStream_t st, bool attr_only, const UwGroup *gdesc = NULL, int32_t n_g = 0)
@@ -4021,21 +4141,25 @@ uw_launch_cp(const s3a_uttdec_t *ud, const UwGeom &q, int32_t n, int32_t f0, hip
         if (!attr_only) hipLaunchKernelGGL(kern, dim3(q.grid), dim3(NT), q.lds, st, ud->d_lanes, ud->S, n, f0, ud->S.win_K, q.fpc,        \
                            q.n_chunks, q.n_tiles, gdesc, n_g); } while (0)
     if (q.nt == 512) { if (q.tab_lds) UW_GO(true, 512); else UW_GO(false, 512); }
+    else if (q.tab_lds) UW_GO(true, 256);       /* (the companion shape) */
     else UW_GO(false, 256);
 #undef UW_GO
     return hipGetLastError();
 }
 
 static int32_t
-uw_launch(const s3a_uttdec_t *ud, int32_t n, int32_t f0, bool attr_only = false, const UwGroup *gdesc = NULL, int32_t n_g = 0)
+uw_launch(s3a_uttdec_t *ud, int32_t n, int32_t f0, bool attr_only = false, const UwGroup *gdesc = NULL, int32_t n_g = 0, bool companion = false,
+          hipStream_t st = NULL)
 {
-    /* (gdesc: n_g groups of 8 frames from the host's table instead of the lanes' windows) */
-    const UwGeom q = uw_geometry(ud, n, gdesc ? n_g * UW_FB : 0);
+    /* (gdesc: n_g groups of 8 frames from the host's table instead of the lanes' windows; companion: the shape that fits beside the search;
+     * st: the stream, the engine's unless given) */
+    const UwGeom q = companion && gdesc ? uw_geometry_companion(ud, n_g * UW_FB) : uw_geometry(ud, n, gdesc ? n_g * UW_FB : 0);
+    if (!st) st = ud->stream;
     hipError_t e;
-#define UW_CASE(cp) case cp: e = ud->exact ? uw_launch_cp<cp, true>(ud, q, n, f0, ud->stream, attr_only, gdesc, n_g) : uw_launch_cp<cp, false>(ud, q, n, f0, ud->stream, attr_only, gdesc, n_g); break
+#define UW_CASE(cp) case cp: e = ud->exact ? uw_launch_cp<cp, true>(ud, q, n, f0, st, attr_only, gdesc, n_g) : uw_launch_cp<cp, false>(ud, q, n, f0, st, attr_only, gdesc, n_g); break
     switch (ud->S.CP) {
     UW_CASE(1); UW_CASE(2); UW_CASE(4); UW_CASE(8); UW_CASE(16); UW_CASE(32);
-    default: e = ud->exact ? uw_launch_cp<64, true>(ud, q, n, f0, ud->stream, attr_only, gdesc, n_g) : uw_launch_cp<64, false>(ud, q, n, f0, ud->stream, attr_only, gdesc, n_g); break;
+    default: e = ud->exact ? uw_launch_cp<64, true>(ud, q, n, f0, st, attr_only, gdesc, n_g) : uw_launch_cp<64, false>(ud, q, n, f0, st, attr_only, gdesc, n_g); break;
     }
 #undef UW_CASE
     if (e != hipSuccess) { s3a_set_error("ku_score_window launch failed: %s", hipGetErrorString(e)); return S3A_EHIP; }
@@ -4262,37 +4386,42 @@ kf_choose_c(s3a_uttdec_t *ud, int32_t n)
     return max(1, min(min(C, KF_MAXC), usable / lanes_per_xcd));
 }
 
-/* n: lane slots of the launch (lanes 0 .. n - 1, or -- J.resume -- that many places of the relay's list); C: workgroups per lane */
+/* n: lane slots of the launch (lanes 0 .. n - 1, or -- J.resume -- that many places of the relay's list); C: workgroups per lane; st: the
+ * stream (NULL: the engine's) */
 template <int NE, bool EXACT, bool HEUR = false>
 static int32_t
-kf_launch_t(s3a_uttdec_t *ud, int32_t n, const KfJob &J, int32_t C)
+kf_launch_t(s3a_uttdec_t *ud, int32_t n, const KfJob &J, int32_t C, hipStream_t st)
 {
     auto kern = ku_frames<NE, EXACT, HEUR>;
     const int32_t lanes_per_xcd = (n + 7) / 8;
+    if (!st) st = ud->stream;
     if (!J.resume) ud->kf_last_c = C;
     const int32_t grid = C == 1 ? n : 8 * C * lanes_per_xcd;
-    if (C > 1) HIPCHK(hipMemsetAsync(ud->d_kfbar, 0, (size_t)ud->n_lanes * 8, ud->stream));
+    if (C > 1) HIPCHK(hipMemsetAsync(ud->d_kfbar, 0, (size_t)ud->n_lanes * 8, st));
     /* the launch's shared arguments: a slot of a small ring (pinned + device) so that launches may queue up behind one another */
-    if (ud->kf_arg_at > 0 && ud->kf_arg_at % KF_ARG_SLOTS == 0) HIPCHK(hipStreamSynchronize(ud->stream));
+    if (ud->kf_arg_at > 0 && ud->kf_arg_at % KF_ARG_SLOTS == 0) {
+        HIPCHK(hipStreamSynchronize(ud->stream));
+        if (ud->kf_stream2) HIPCHK(hipStreamSynchronize(ud->kf_stream2));
+    }
     KfArgs *ha = (KfArgs *)ud->h_kfargs + ud->kf_arg_at % KF_ARG_SLOTS, *da = (KfArgs *)ud->d_kfargs + ud->kf_arg_at % KF_ARG_SLOTS;
     ud->kf_arg_at++;
     ha->S = ud->S; ha->lm = ud->lm->d; ha->dict = ud->dict; ha->par = ud->par; ha->J = J;
-    HIPCHK(hipMemcpyAsync(da, ha, sizeof(KfArgs), hipMemcpyHostToDevice, ud->stream));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(KF_NT), 0, ud->stream, ud->d_lanes, (const KfArgs *)da, n, C,
+    HIPCHK(hipMemcpyAsync(da, ha, sizeof(KfArgs), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(KF_NT), 0, st, ud->d_lanes, (const KfArgs *)da, n, C,
                        ud->d_kfbar, (ud->weak_possible ? 1 : 0) | (ud->big_wl ? 2 : 0), ud->persist < 3 ? 1 : 0);
     HIPCHK(hipGetLastError());
     return S3A_OK;
 }
 
 static int32_t
-kf_launch_c(s3a_uttdec_t *ud, int32_t n, const KfJob &J, int32_t C)
+kf_launch_c(s3a_uttdec_t *ud, int32_t n, const KfJob &J, int32_t C, hipStream_t st = NULL)
 {
     if (ud->S.ne == 5) {
-        if (ud->S.pheurtype > 0) return ud->exact ? kf_launch_t<5, true, true>(ud, n, J, C) : kf_launch_t<5, false, true>(ud, n, J, C);
-        return ud->exact ? kf_launch_t<5, true>(ud, n, J, C) : kf_launch_t<5, false>(ud, n, J, C);
+        if (ud->S.pheurtype > 0) return ud->exact ? kf_launch_t<5, true, true>(ud, n, J, C, st) : kf_launch_t<5, false, true>(ud, n, J, C, st);
+        return ud->exact ? kf_launch_t<5, true>(ud, n, J, C, st) : kf_launch_t<5, false>(ud, n, J, C, st);
     }
-    if (ud->S.pheurtype > 0) return ud->exact ? kf_launch_t<3, true, true>(ud, n, J, C) : kf_launch_t<3, false, true>(ud, n, J, C);
-    return ud->exact ? kf_launch_t<3, true>(ud, n, J, C) : kf_launch_t<3, false>(ud, n, J, C);
+    if (ud->S.pheurtype > 0) return ud->exact ? kf_launch_t<3, true, true>(ud, n, J, C, st) : kf_launch_t<3, false, true>(ud, n, J, C, st);
+    return ud->exact ? kf_launch_t<3, true>(ud, n, J, C, st) : kf_launch_t<3, false>(ud, n, J, C, st);
 }
 
 /* one launch, the cluster size the library's (KF_WINDOW blocks; a call without the relay) */
@@ -4307,11 +4436,59 @@ kf_launch(s3a_uttdec_t *ud, int32_t n, const KfJob &J)
  * at their next frame boundary and the next launch -- enqueued here, up front, behind the first -- continues them that way.  A launch of
  * the chain that is handed nothing ends at once.  Only an engine that may size clusters for the whole device plans a chain (kf_alone; not
  * with s3a_uttdec_opts_t.cluster set: the caller's cluster size holds for the whole call); s3a_variants_t.kf_no_relay: never. */
+/* SCORING BESIDE THE SEARCH: the chain's first launch as three, over two streams (KfOverlap: kf_decode_queue, which has scored the first
+ * n1 takes' utterances on the engine's stream and set *q_ready = n1).
+ *   engine stream   ku_frames #1: lanes 0 .. n1 - 1, one workgroup each -- half a CU each (NOT one per CU: of the bench's 256 CUs 87 were
+ *                   seen with two of the 256 lanes, 82 with one, 87 with none; the companion's workgroups take whatever halves are free,
+ *                   two of them fit a CU as well);
+ *   second stream   behind the first utterances' scoring: the COMPANION scoring of groups [g0, g0 + n_g) in the CUs' other halves, then
+ *                   *q_ready = n_utt, then ku_frames #2 over ALL n lanes: lanes n1 .. n - 1 start; of lanes 0 .. n1 - 1 one that LEFT #1
+ *                   because its next take was not scored yet goes on taking, and the workgroup of one still at work in #1 (it will find
+ *                   everything scored) ends at once.  (A launch on the engine's stream behind #1 would hold the lanes that left until #1's
+ *                   LAST lane is through -- the end of the queue: measured, profiles/r7_overlap_experiments.txt.)
+ * The engine's stream then waits for the second one: what follows (the relay's launches, the call's close) is behind both.  Nothing on the
+ * device waits for another kernel: the order is the streams' and the events', and a lane changes hands by one compare-and-swap on its flag
+ * (KfJob.lane_left). */
+struct KfOverlap { int32_t n1; size_t g0, n_g; const size_t *g_end; };      /* (g_end[k]: the groups up to and with the k-th take's utterance) */
+#define SB_PIECE 1024
+static void kf_mark(s3a_uttdec_t *ud, hipStream_t st);
 static int32_t
-kf_launch_chain(s3a_uttdec_t *ud, int32_t n, KfJob J)
+kf_launch_overlapped(s3a_uttdec_t *ud, int32_t n, KfJob J, const KfOverlap &ov)
 {
-    /* (kf_relay_at, the tests' switch: the chain from one workgroup per lane on, however few the lanes) */
-    const int32_t C0 = s3a_variants()->kf_relay_at > 0 && ud->kf_cluster_opt == 0 ? 1 : kf_choose_c(ud, n), usable = kf_usable_per_xcd(ud), W = KF_ST_WORDS + ud->n_lanes;
+    hipStream_t s1 = ud->stream, s2 = ud->kf_stream2;
+    int32_t rc;
+    J.q_ready = ud->d_kfnext + 1; J.n_resumed = ud->d_kfnext + 2; J.lane_left = ud->d_kfleft;
+    J.n1 = ov.n1;
+    HIPCHK(hipEventRecord(ud->kf_ov_ev[0], s1));
+    J.ov = 1;
+    if ((rc = kf_launch_c(ud, ov.n1, J, 1, s1)) != S3A_OK) return rc;
+    HIPCHK(hipStreamWaitEvent(s2, ud->kf_ov_ev[0], 0));
+    /* (*q_ready follows the scoring launch by launch: the groups are in the order of the takes, and the companion scores utterances faster
+     * than the first lanes decode them -- a lane of #1 that is through with its utterance finds the next ones scored and stays; with one
+     * step to n_utt at the end 239 of 256 lanes left and idled until then, profiles/r7_overlap_experiments.txt) */
+    int32_t ready = ov.n1;
+    for (size_t g = 0; g < ov.n_g; g += SB_PIECE) {
+        const size_t m = min((size_t)SB_PIECE, ov.n_g - g);
+        if ((rc = uw_launch(ud, 0, 0, false, ud->sb_gdesc.d + ov.g0 + g, (int32_t)m, true, s2)) != S3A_OK) return rc;
+        ud->kf_n_score++;
+        const int32_t was = ready;
+        while (ready < J.n_utt && ov.g_end[ready] <= ov.g0 + g + m) ready++;
+        if (ready > was) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(ud->d_kfnext + 1), ready, 1, s2));
+    }
+    kf_mark(ud, s2);                                    /* (the last scoring launch's end: kf_collect) */
+    if (ready < J.n_utt) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(ud->d_kfnext + 1), J.n_utt, 1, s2));
+    J.ov = 2;
+    if ((rc = kf_launch_c(ud, n, J, 1, s2)) != S3A_OK) return rc;
+    HIPCHK(hipEventRecord(ud->kf_ov_ev[1], s2));
+    HIPCHK(hipStreamWaitEvent(s1, ud->kf_ov_ev[1], 0));
+    return S3A_OK;
+}
+
+static int32_t
+kf_launch_chain(s3a_uttdec_t *ud, int32_t n, KfJob J, const KfOverlap *ov = NULL)
+{
+    /* (kf_relay_at, the tests' switch: the chain from one workgroup per lane on, however few the lanes; scoring beside the search: one per lane) */
+    const int32_t C0 = (s3a_variants()->kf_relay_at > 0 && ud->kf_cluster_opt == 0) || ov ? 1 : kf_choose_c(ud, n), usable = kf_usable_per_xcd(ud), W = KF_ST_WORDS + ud->n_lanes;
     int32_t st_c[KF_STAGES], st_cap[KF_STAGES], n_st = 0;
     /* (kf_relay_at, the tests' switch: the chain whatever else runs on the device -- the caller answers for co-residency, as with .cluster) */
     if (ud->d_kfrelay && ud->kf_cluster_opt == 0 && (kf_alone(ud) || s3a_variants()->kf_relay_at > 0) && !s3a_variants()->kf_no_relay) {
@@ -4324,7 +4501,7 @@ kf_launch_chain(s3a_uttdec_t *ud, int32_t n, KfJob J)
             prev_n = cap; prev_c = c;
         }
     }
-    if (n_st == 0) return kf_launch_c(ud, n, J, C0);
+    if (n_st == 0) return ov ? kf_launch_overlapped(ud, n, J, *ov) : kf_launch_c(ud, n, J, C0);
     HIPCHK(hipMemsetAsync(ud->d_kfrelay, 0, ((size_t)(KF_STAGES + 1) * W + (size_t)3 * ud->n_lanes) * 4, ud->stream));
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)ud->d_kfrelay, n, 1, ud->stream));           /* (the first launch's lanes at work) */
     J.lane_f = ud->d_kfrelay + (size_t)(KF_STAGES + 1) * W; J.lane_uq = J.lane_f + ud->n_lanes; J.lane_stop = J.lane_uq + ud->n_lanes;
@@ -4332,7 +4509,10 @@ kf_launch_chain(s3a_uttdec_t *ud, int32_t n, KfJob J)
     for (int32_t k = 0; k <= n_st && rc == S3A_OK; k++) {
         J.resume = k > 0; J.stop_at = k < n_st ? st_cap[k] : 0;
         J.st_cur = ud->d_kfrelay + (size_t)k * W; J.st_next = ud->d_kfrelay + (size_t)(k + 1) * W;
-        rc = kf_launch_c(ud, k == 0 ? n : st_cap[k - 1], J, k == 0 ? C0 : st_c[k - 1]);
+        /* (scoring beside the search: the relay's counters span the two launches that stand for the first -- a lane that left for want of
+         * scores counts as at work, and only a lane that found the QUEUE empty counts itself out, so no hand-over begins before the last take) */
+        if (k == 0 && ov) rc = kf_launch_overlapped(ud, n, J, *ov);
+        else rc = kf_launch_c(ud, k == 0 ? n : st_cap[k - 1], J, k == 0 ? C0 : st_c[k - 1]);
     }
     ud->kf_n_relay = n_st;
     return rc;
@@ -4353,21 +4533,30 @@ enqueue_block(s3a_uttdec_t *ud, int32_t n, int32_t fg0, int32_t nf)
 
 /* a time mark on the engine's stream (pairs of them bracket the scoring launches and ku_frames: kf_collect) */
 static void
-kf_mark(s3a_uttdec_t *ud)
+kf_mark(s3a_uttdec_t *ud, hipStream_t st = NULL)
 {
     if ((size_t)ud->kf_ev_n >= ud->kf_evs.size()) {
         hipEvent_t e = NULL;
         if (hipEventCreate(&e) != hipSuccess) return;
         ud->kf_evs.push_back(e);
     }
-    (void)hipEventRecord(ud->kf_evs[ud->kf_ev_n++], ud->stream);
+    (void)hipEventRecord(ud->kf_evs[ud->kf_ev_n++], st ? st : ud->stream);
 }
 
-/* behind the stream's synchronisation: marks come in triples (before scoring, between, behind ku_frames) */
+/* behind the stream's synchronisation: marks come in triples (before scoring, between, behind ku_frames) -- or, from a call that scored
+ * beside the search, as four: before the first scoring launch, before the first ku_frames, behind the last scoring launch (second stream),
+ * behind the last ku_frames; the two spans then OVERLAP */
 static void
 kf_collect(s3a_uttdec_t *ud)
 {
     ud->kf_score_ms = ud->kf_frames_ms = 0.0;
+    if (ud->kf_overlapped && ud->kf_ev_n == 4) {
+        float a = 0.0f, b = 0.0f;
+        if (hipEventElapsedTime(&a, ud->kf_evs[0], ud->kf_evs[2]) == hipSuccess) ud->kf_score_ms = a;
+        if (hipEventElapsedTime(&b, ud->kf_evs[1], ud->kf_evs[3]) == hipSuccess) ud->kf_frames_ms = b;
+        ud->kf_ev_n = 0;
+        return;
+    }
     for (int32_t i = 0; i + 2 < ud->kf_ev_n; i += 3) {
         float a = 0.0f, b = 0.0f;
         if (hipEventElapsedTime(&a, ud->kf_evs[i], ud->kf_evs[i + 1]) == hipSuccess) ud->kf_score_ms += a;
@@ -4406,14 +4595,16 @@ sb_reserve(s3a_uttdec_t *ud, size_t rows, size_t groups, size_t n_utt)
     return S3A_OK;
 }
 
-/* the groups of utterances [u0, u1): 8 consecutive frames each, rows from `row` on; returns the groups written */
+/* the groups of utterances [u0, u1): 8 consecutive frames each, rows from `row` on; returns the groups written
+ * (order: the utterances order[u0 .. u1) in that order -- rows and groups then follow the order of the takes) */
 static size_t
-sb_describe(s3a_uttdec_t *ud, const float *const *feat_dev, const int32_t *n_frames, int32_t u0, int32_t u1, size_t g_at)
+sb_describe(s3a_uttdec_t *ud, const float *const *feat_dev, const int32_t *n_frames, int32_t u0, int32_t u1, size_t g_at, const int32_t *order = NULL)
 {
     const size_t S_ = (size_t)ud->S.n_sen;
     const int32_t DP = ud->S.D4 * 4;
     size_t row = 0, g = g_at;
-    for (int32_t u = u0; u < u1; u++) {
+    for (int32_t k = u0; k < u1; k++) {
+        const int32_t u = order ? order[k] : k;
         ud->sb_row0.h[u] = (long long)row;
         for (int32_t j0 = 0; j0 < n_frames[u]; j0 += UW_FB, g++) {
             UwGroup &gr = ud->sb_gdesc.h[g];
@@ -4428,12 +4619,13 @@ sb_describe(s3a_uttdec_t *ud, const float *const *feat_dev, const int32_t *n_fra
 }
 
 /* score the groups [g0, g0 + n_g) of the uploaded table: launches of up to SB_PIECE groups */
-#define SB_PIECE 1024
 static int32_t
-sb_score(s3a_uttdec_t *ud, size_t g0, size_t n_g)
+sb_score(s3a_uttdec_t *ud, size_t g0, size_t n_g, bool companion = false, hipStream_t st = NULL)
 {
+    /* (companion: the shape that fits a CU beside a ku_frames workgroup -- beside the search, or, s3a_variants_t.uw_companion, for every pass) */
+    companion = companion || s3a_variants()->uw_companion != 0;
     for (size_t g = 0; g < n_g; g += SB_PIECE) {
-        const int32_t rc = uw_launch(ud, 0, 0, false, ud->sb_gdesc.d + g0 + g, (int32_t)min((size_t)SB_PIECE, n_g - g));
+        const int32_t rc = uw_launch(ud, 0, 0, false, ud->sb_gdesc.d + g0 + g, (int32_t)min((size_t)SB_PIECE, n_g - g), companion, st);
         if (rc != S3A_OK) return rc;
         ud->kf_n_score++;
     }
@@ -4496,10 +4688,6 @@ kf_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat_dev, c
     if (max_rows > budget) { s3a_set_error("s3a_uttdec_decode_queue: an utterance's scores (%zu rows) do not fit the device", max_rows); return S3A_ENOMEM; }
     int32_t rc;
     if ((rc = sb_reserve(ud, max_rows, groups, (size_t)n_utt)) != S3A_OK) return rc;
-    std::vector<size_t> g_at(cut.size(), 0);
-    for (size_t k = 0; k + 1 < cut.size(); k++) g_at[k + 1] = g_at[k] + sb_describe(ud, feat_dev, n_frames, cut[k], cut[k + 1], g_at[k]);
-    HIPCHK(hipMemcpyAsync(ud->sb_gdesc.d, ud->sb_gdesc.h, g_at.back() * sizeof(UwGroup), hipMemcpyHostToDevice, ud->stream));
-    HIPCHK(hipMemcpyAsync(ud->sb_row0.d, ud->sb_row0.h, (size_t)n_utt * 8, hipMemcpyHostToDevice, ud->stream));
     /* the order of the takes: within a part the longest utterance first (stable: equal lengths in queue order) -- the launch ends with its
      * slowest lane, and an utterance taken when the counter is nearly through should be a short one */
     if ((rc = q_reserve(ud, ud->kf_order, S3A_GROW_DEV | S3A_GROW_PIN, (size_t)n_utt, "queue order")) != S3A_OK) return rc;
@@ -4508,20 +4696,71 @@ kf_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat_dev, c
         if (!s3a_variants()->kf_queue_in_order)
             std::stable_sort(ud->kf_order.h + cut[k], ud->kf_order.h + cut[k + 1], [&](int32_t a, int32_t b) { return n_frames[a] > n_frames[b]; });
     }
+    /* SCORING BESIDE THE SEARCH (kf_launch_overlapped): only the first n1 takes' utterances are scored up front; the rest is scored by the
+     * companion shape in the halves of the CUs that n1 lanes leave free, and the other lanes start when it is through.  Only where the plan's
+     * premise holds -- an engine that sizes its launches for the whole device (as the relay), two lanes per CU, more utterances than lanes --
+     * and only for the plain call: one part, no second pass, no look-ahead heuristic, no kept lattices.  s3a_variants_t: kf_overlap = 1
+     * asks for it (KF_OVERLAP_DEFAULT: without being asked), kf_overlap_n1 > 0 forces it with that many first lanes (the tests' small
+     * engines; the caller answers for co-residency), kf_no_overlap: never. */
+    const s3a_variants_t *va = s3a_variants();
+    int32_t n1 = 0;
+    if (!va->kf_no_overlap && cut.size() == 2 && !ud->dag && ud->S.pheurtype == 0 && !ud->q_keep_lat && n_utt > ud->n_lanes && ud->kf_cluster_opt == 0
+        && ud->d_kfleft) {
+        const int32_t n_cu = max(1, ud->g->dev->n_cu);
+        if (va->kf_overlap_n1 > 0) { if (va->kf_overlap_n1 < ud->n_lanes) n1 = va->kf_overlap_n1; }
+        else if ((KF_OVERLAP_DEFAULT || va->kf_overlap) && kf_alone(ud) && ud->n_lanes > n_cu && ud->n_lanes / 2 <= n_cu && kf_choose_c(ud, ud->n_lanes) == 1)
+            n1 = ud->n_lanes / 2;
+    }
+    if (n1 > 0) {
+        if (!ud->kf_stream2 && hipStreamCreateWithFlags(&ud->kf_stream2, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ud->kf_stream2 = NULL; n1 = 0; }
+        for (auto &e : ud->kf_ov_ev)
+            if (n1 > 0 && !e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); e = NULL; n1 = 0; }
+    }
+    ud->kf_overlapped = n1 > 0 ? 1 : 0;
+    std::vector<size_t> g_at(cut.size(), 0), g_end;
+    size_t g_first = 0;             /* (the plan: the groups of the first n1 takes' utterances) */
+    if (n1 > 0) {
+        g_first = sb_describe(ud, feat_dev, n_frames, 0, n1, 0, ud->kf_order.h);
+        /* (one run of rows over both pieces: the second piece's rows go on where the first one's end) */
+        const size_t rows1 = (size_t)ud->sb_row0.h[ud->kf_order.h[n1 - 1]] + (size_t)n_frames[ud->kf_order.h[n1 - 1]];
+        g_at[1] = g_first + sb_describe(ud, feat_dev, n_frames, n1, n_utt, g_first, ud->kf_order.h);
+        for (int32_t k = n1; k < n_utt; k++) ud->sb_row0.h[ud->kf_order.h[k]] += (long long)rows1;
+        for (size_t g = g_first; g < g_at[1]; g++) { ud->sb_gdesc.h[g].win += rows1 * (size_t)ud->S.n_sen; ud->sb_gdesc.h[g].winb += rows1 * (size_t)ud->S.n_sen; }
+        g_end.resize((size_t)n_utt);
+        size_t gq = 0;
+        for (int32_t k = 0; k < n_utt; k++) { gq += (size_t)(n_frames[ud->kf_order.h[k]] + UW_FB - 1) / UW_FB; g_end[k] = gq; }
+        /* (the launches' argument slots: none of this call's launches may have to wait for a slot -- the host would wait for ku_frames #1 with
+         * the companion's launches still in its hands) */
+        if (ud->kf_arg_at % KF_ARG_SLOTS + 2 + KF_STAGES > KF_ARG_SLOTS) {
+            HIPCHK(hipStreamSynchronize(ud->stream));
+            HIPCHK(hipStreamSynchronize(ud->kf_stream2));
+            ud->kf_arg_at = 0;
+        }
+    }
+    else
+        for (size_t k = 0; k + 1 < cut.size(); k++) g_at[k + 1] = g_at[k] + sb_describe(ud, feat_dev, n_frames, cut[k], cut[k + 1], g_at[k]);
+    HIPCHK(hipMemcpyAsync(ud->sb_gdesc.d, ud->sb_gdesc.h, g_at.back() * sizeof(UwGroup), hipMemcpyHostToDevice, ud->stream));
+    HIPCHK(hipMemcpyAsync(ud->sb_row0.d, ud->sb_row0.h, (size_t)n_utt * 8, hipMemcpyHostToDevice, ud->stream));
     HIPCHK(hipMemcpyAsync(ud->kf_order.d, ud->kf_order.h, (size_t)n_utt * 4, hipMemcpyHostToDevice, ud->stream));
     ud->kf_n_score = ud->kf_n_frames = 0;
     for (size_t k = 0; k + 1 < cut.size(); k++) {
         const int32_t u0 = cut[k], nu = cut[k + 1] - cut[k];
         kf_mark(ud);
-        if ((rc = sb_score(ud, g_at[k], g_at[k + 1] - g_at[k])) != S3A_OK) return rc;
+        if ((rc = sb_score(ud, g_at[k], n1 > 0 ? g_first : g_at[k + 1] - g_at[k])) != S3A_OK) return rc;
         kf_mark(ud);
-        HIPCHK(hipMemsetAsync(ud->d_kfnext, 0, 4, ud->stream));
+        if (n1 > 0) {               /* (the counter, *q_ready = n1, the resumed lanes' count; no lane has left) */
+            HIPCHK(hipMemsetAsync(ud->d_kfnext, 0, 16 * 4, ud->stream));
+            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(ud->d_kfnext + 1), n1, 1, ud->stream));
+            HIPCHK(hipMemsetAsync(ud->d_kfleft, 0, (size_t)ud->n_lanes * 4, ud->stream));
+        }
+        else HIPCHK(hipMemsetAsync(ud->d_kfnext, 0, 4, ud->stream));
         KfJob J;
         memset(&J, 0, sizeof J);
         J.mode = KF_QUEUE; J.n_utt = nu; J.u0 = u0; J.order = ud->kf_order.d; J.next = ud->d_kfnext; J.lane_u = ud->d_kfnext + 16; J.stage = ud->q_ctx.d;
         J.row0 = ud->sb_row0.d; J.scores = ud->sb_scores.d; J.bests = ud->sb_bests.d;
         J.hdr = ud->q_hdr.d; J.words = ud->q_words.d; J.wcount = wcount; J.P = P; J.B = B; J.n_word = ud->cfg.n_word;
-        if ((rc = kf_launch_chain(ud, min(ud->n_lanes, nu), J)) != S3A_OK) return rc;
+        const KfOverlap ov = { n1, g_first, g_at[1] - g_first, g_end.data() };
+        if ((rc = kf_launch_chain(ud, min(ud->n_lanes, nu), J, n1 > 0 ? &ov : NULL)) != S3A_OK) return rc;
         ud->kf_n_frames++;
         kf_mark(ud);
     }
@@ -4683,7 +4922,7 @@ uttdec_decode(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, const i
     HIPCHK(hipSetDevice(ud->device));
     int32_t rc, maxT = 0;
     ud->q_n = 0;
-    ud->kf_n_score = ud->kf_n_frames = ud->kf_last_c = ud->kf_n_relay = 0;         /* (s3a_uttdec_last_parts: all zero unless THIS call goes through ku_frames) */
+    ud->kf_n_score = ud->kf_n_frames = ud->kf_last_c = ud->kf_n_relay = ud->kf_overlapped = 0;         /* (s3a_uttdec_last_parts: all zero unless THIS call goes through ku_frames) */
     double tm[6] = { 0, 0, 0, 0, 0, 0 };
     auto now = []() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; };
     tm[0] = now();
@@ -4881,7 +5120,7 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
         return S3A_EINVAL;
     }
     HIPCHK(hipSetDevice(ud->device));
-    ud->kf_n_score = ud->kf_n_frames = ud->kf_last_c = ud->kf_n_relay = 0;
+    ud->kf_n_score = ud->kf_n_frames = ud->kf_last_c = ud->kf_n_relay = ud->kf_overlapped = 0;
     const UShared &S = ud->S;
     const bool graph_mode = ud->use_graph && ud->prof_every == 0;
     /* ku_frames (KF_QUEUE): the lanes take the utterances themselves -- no schedule, no refill events, no window boundaries */
@@ -5199,6 +5438,21 @@ extern "C" int32_t
 s3a_uttdec_last_relay(const s3a_uttdec_t *ud)
 {
     return ud ? ud->kf_n_relay : 0;
+}
+
+extern "C" int32_t
+s3a_uttdec_last_overlap(s3a_uttdec_t *ud, int32_t *overlapped, int32_t *resumed)
+{
+    if (!ud) return S3A_EINVAL;
+    if (overlapped) *overlapped = ud->kf_overlapped;
+    if (resumed) {
+        *resumed = 0;
+        if (ud->kf_overlapped) {
+            HIPCHK(hipSetDevice(ud->device));
+            HIPCHK(hipMemcpy(resumed, ud->d_kfnext + 2, 4, hipMemcpyDeviceToHost));
+        }
+    }
+    return S3A_OK;
 }
 
 extern "C" int32_t

@@ -811,6 +811,11 @@ int32_t s3a_uttdec_wl_ticks(s3a_uttdec_t *ud, int32_t lane, long long *out16);
  * up-front scoring (ku_score_window: milliseconds, launches) and ku_frames itself; *cluster = workgroups per lane.  All zero when
  * the call ran the frame as separate launches (fewer lanes than pay for ku_frames, an option it does not serve, persist = -1). */
 int32_t s3a_uttdec_last_parts(s3a_uttdec_t *ud, double *score_ms, int32_t *n_score, double *frames_ms, int32_t *n_frames, int32_t *cluster);
+/* ... a queue that was scored BESIDE the search (s3a_variants_t.kf_overlap ...): *overlapped = 1, and then score_ms spans the first scoring
+ * launch's start to the last one's end, frames_ms the first ku_frames launch's start to the last one's end -- the two spans OVERLAP, their
+ * sum is more than the call took.  *resumed: lanes that found their next utterance not scored yet, left their launch and were taken up again
+ * by the launch behind the scoring. */
+int32_t s3a_uttdec_last_overlap(s3a_uttdec_t *ud, int32_t *overlapped, int32_t *resumed);
 int32_t s3a_uttdec_frame_ticks(s3a_uttdec_t *ud, int32_t lane, long long *out16, int32_t *cluster);
 /* diagnostics: launches the last call's RELAY had behind its first (0: one launch to the end).  A ku_frames call ends with its slowest
  * lane; when no utterance is left to take and few lanes are still at work, they hand over at a frame boundary to a launch that continues
@@ -1243,6 +1248,16 @@ typedef struct {
                                      * still at work, they hand over at a frame boundary to a launch that runs them as clusters of 2, then 4 workgroups) */
     int32_t kf_relay_at;            /* > 0: the relay's first hand-over when that many lanes are left, the second at half of it (default: as many as
                                      * fill the chip as clusters of 2 / of 4; tests use it to run the chain with a handful of lanes) */
+    /* ku_frames' queue, SCORING BESIDE THE SEARCH: only the first half of the lanes' utterances are scored up front; the rest is scored by a
+     * companion shape of the scoring kernel in the halves of the CUs that those lanes leave free, and the other lanes start behind it.  Only
+     * for the plain call of an engine alone on its device with two lanes per CU (one part, no second pass, no -pheurtype, no kept lattices,
+     * more utterances than lanes); every other call is enqueued as before. */
+    int32_t kf_no_overlap;          /* never (A/B) */
+    int32_t kf_overlap;             /* where the library does not do it by default: do it where the conditions hold */
+    int32_t kf_overlap_n1;          /* > 0: do it whatever the engine's size and whatever else runs on the device, with that many first lanes (< lanes;
+                                     * tests use it with a handful of lanes; the call's own conditions still hold) */
+    int32_t uw_companion;           /* the up-front scoring passes of ku_frames' calls through the companion shape (256 threads, the LDS a CU has left
+                                     * beside a ku_frames workgroup): the same rows, for tests without any concurrency */
 } s3a_variants_t;
 void    s3a_variants_default(s3a_variants_t *v);
 void    s3a_get_variants(s3a_variants_t *v);            /* the variants in force (read-modify-write with s3a_set_variants) */

@@ -28,9 +28,14 @@ def main():
     ap.add_argument("--engines", type=int, default=1)
     ap.add_argument("--sample", type=int, default=8, help="lanes whose clocks are averaged")
     ap.add_argument("--placement", action="store_true", help="lock-step decode of --lanes utterances; per lane when and where the launch at frame 512 ran")
+    ap.add_argument("--overlap", action="store_true", help="the batch as one queue, scored beside the search (one engine): where the first launch's lanes "
+                    "(0 .. lanes/2 - 1) and the second launch's ran (XCC_ID + HW_ID's SE / SH / CU), when they started and ended, how many left and were resumed")
+    ap.add_argument("--variant", action="append", default=[], metavar="FIELD=INT", help="a field of s3a_variants_t")
     args = ap.parse_args()
     from cmusphinx_amd import bundle, lib, s3io, synth_task
     L = lib.load()
+    if args.variant:
+        lib.set_variants(**{kv.split('=')[0]: int(kv.split('=')[1]) for kv in args.variant})
     d = os.path.join(tempfile.gettempdir(), f"s3a_kf_{args.utts}_{args.frames}")
     bpath = os.path.join(d, "decoder.bundle")
     if not os.path.exists(bpath):
@@ -79,6 +84,28 @@ def main():
                           "dur_us": {"min": float((ends - starts).min()), "p50": float(np.median(ends - starts)), "p90": float(np.percentile(ends - starts, 90)), "max": float((ends - starts).max())},
                           "end_us_max": float(ends.max()), "distinct_cus": len(cu), "lanes_per_cu_hist": {str(k): per.count(k) for k in sorted(set(per))},
                           "late_starters": [(int(z), round(float(starts[z]), 1)) for z in np.argsort(-starts)[:8]]}))
+        return
+    if args.overlap:
+        def cu_of(r):
+            return (r[3] & 0xf, (r[2] >> 13) & 7, (r[2] >> 12) & 1, (r[2] >> 8) & 15)
+        for step in range(args.steps + 1):
+            ms = decs[0].ud.decode_queue_dev([fdev[k] for k in order], [nfr[k] for k in order], D4x4)
+        rows = [decs[0].ud.frame_dbg(z) for z in range(NLE)]
+        t0 = min(r[0] for r in rows)
+        n1 = NLE // 2
+        out = {"device_ms": round(ms, 1), "parts": decs[0].ud.last_parts(), "overlap": decs[0].ud.last_overlap(), "relay": decs[0].ud.last_relay()}
+        for name, zs in (("first_launch", range(n1)), ("second_launch", range(n1, NLE))):
+            cus = {}
+            for z in zs:
+                cus.setdefault(cu_of(rows[z]), []).append(z)
+            per = sorted(len(v) for v in cus.values())
+            st = np.array([(rows[z][0] - t0) * 1e-5 for z in zs]); en = np.array([(rows[z][1] - t0) * 1e-5 for z in zs])
+            out[name] = {"distinct_cus": len(cus), "lanes_per_cu_hist": {str(k): per.count(k) for k in sorted(set(per))},
+                         "xcds": sorted({c[0] for c in cus}), "start_ms": [round(float(st.min()), 1), round(float(np.median(st)), 1), round(float(st.max()), 1)],
+                         "end_ms": [round(float(en.min()), 1), round(float(np.median(en)), 1), round(float(en.max()), 1)]}
+        a = {cu_of(rows[z]) for z in range(n1)}; b = {cu_of(rows[z]) for z in range(n1, NLE)}
+        out["cus_with_a_lane_of_each_launch"] = len(a & b)
+        print(json.dumps(out))
         return
     best = None
     for step in range(args.steps + 1):
