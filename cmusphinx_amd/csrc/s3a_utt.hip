@@ -1627,6 +1627,10 @@ enum { KF_WINDOW, KF_STATIC, KF_QUEUE };
 #ifndef KF_OVERLAP_DEFAULT
 #define KF_OVERLAP_DEFAULT 1    /* scoring beside the search without being asked (kf_decode_queue; profiles/r7_overlap_experiments.txt) */
 #endif
+#ifndef KF_OVERLAP_LEAD
+#define KF_OVERLAP_LEAD 128     /* ... frames of each of the first utterances scored before the search begins (a multiple of 8; measured: at 64 no lane of the
+                                 * bench's 256 first ones asks for an unscored frame, at 32 most do -- one step of margin, profiles/r8_rows_ahead_experiments.txt 2) */
+#endif
 #define KF_STAGES 2             /* launches a call's relay may have behind its first */
 
 union KfPool {                  /* phases that never overlap share this LDS */
@@ -1650,6 +1654,8 @@ union KfPool {                  /* phases that never overlap share this LDS */
 struct KfSh {                   /* the workgroup's LDS outside the word level's own arrays */
     KfPool pool;
     int32_t best[2 * WL_MAXT], acc[2 * WL_MAXT], pre[WL_MAXT + 1], red[KF_WAVES], dead, u, u2, dynbeam;
+    int32_t fk, fk2;            /* scoring beside the search: the frames the lane KNOWS to be scored of its utterance (the last *f_ready it read;
+                                 * INT32_MAX: nothing to ask) | what the reload of a frame boundary read */
     ULane Lc;                   /* the lane's structure (its ~60 pointers): a copy in LDS -- a field is a ds_read at a constant address; out of
                                  * memory it was the structure's spilled address back from scratch, then the pointer, then the data: two
                                  * round trips in front of many a step's first access */
@@ -1702,10 +1708,16 @@ struct KfJob {
                                  * n1 that LEFT the first launch goes on (the workgroup of one that did not ends at once) */
     int32_t n1;
     const int32_t *q_ready;     /* [1] takes whose utterances are scored (NULL: all): a lane takes ticket k only if k < *q_ready, else it LEAVES */
-    int32_t *lane_left;         /* [n_lanes] 0: the lane is in the first launch's hands; 1: it left for want of scores (its LAST store of that launch);
-                                 * 2: the second launch's workgroup came, found it at work and went -- one compare-and-swap each, so exactly one
+    int32_t *lane_left;         /* [n_lanes] 0: the lane is in the first launch's hands; 1: it left for want of scores between two utterances, 3: inside one (its LAST store
+                                 * of that launch either way); 2: the second launch's workgroup came, found it at work and went -- one compare-and-swap each, so exactly one
                                  * of the two launches has the lane at any time, and a lane that finds 2 knows that everything is scored */
     int32_t *n_resumed;         /* [1] lanes the second launch took up again */
+    /* ROWS AHEAD: the first n1 takes' utterances are scored in ROUNDS beside the search, a few groups of each per launch (kf_decode_queue) */
+    const int32_t *f_ready;     /* [1] frames [0, min(*f_ready, n_frames)) of EVERY one of the first n1 takes' utterances are scored (NULL: all;
+                                 * INT32_MAX once they are): a lane on one of them that reaches a frame at or beyond it LEAVES at that frame
+                                 * boundary -- lane_f / lane_uq say where, as at the relay's hand-over, and lane_left becomes 3: the second launch's
+                                 * workgroup continues the utterance there */
+    int32_t *n_inside;          /* [1] lanes the second launch took up again INSIDE an utterance */
 };
 
 /* all workgroups of the lane's cluster have finished the phase and see what the others wrote.
@@ -2930,14 +2942,17 @@ ku_frames(const ULane *__restrict__ lanes, const KfArgs *__restrict__ A, int32_t
     if (C == 1) { z = blockIdx.x; r = 0; }
     else { const int32_t b = blockIdx.x, xcd = b & 7, j = b >> 3; z = (j / C) * 8 + xcd; r = j % C; }
     if (z >= n_lanes) return;
+    bool mid_left = false;
     if (J.ov == 2 && z < J.n1) {        /* (the first launch's lane: only one that LEFT goes on here -- what it left is acquired with its flag) */
         if (threadIdx.x == 0) {
             const int32_t was = atomicCAS(&J.lane_left[z], 0, 2);
             sh.u2 = was;
-            if (was == 1) atomicAdd(J.n_resumed, 1);
+            if (was == 1 || was == 3) atomicAdd(J.n_resumed, 1);
+            if (was == 3) atomicAdd(J.n_inside, 1);
         }
         __syncthreads();
-        if (sh.u2 != 1) return;
+        if (sh.u2 != 1 && sh.u2 != 3) return;
+        mid_left = sh.u2 == 3;  /* (it left INSIDE an utterance: lane_uq / lane_f) */
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         __syncthreads();
     }
@@ -2950,7 +2965,7 @@ ku_frames(const ULane *__restrict__ lanes, const KfArgs *__restrict__ A, int32_t
     for (int32_t i = tid; i < (int32_t)(sizeof(ULane) / 4); i += KF_NT) ((int32_t *)&sh.Lc)[i] = ((const int32_t *)&lanes[z])[i];
     const ULane &L = sh.Lc;
     UCtx *ctx = S.ctx_all + z;
-    if (tid == 0) sh.dead = 0;
+    if (tid == 0) { sh.dead = 0; sh.fk = J.f_ready ? 0 : INT32_MAX; }      /* (0: the first gated frame asks) */
     if (tid < 16) sh.kacc[tid] = 0;
     for (int32_t i = tid; i < KF_SENBITS / 32; i += KF_NT) sh.senbits[i] = 0u;
     if (tid <= S.T) sh.nb[tid] = S.node_base[tid];
@@ -2973,7 +2988,7 @@ ku_frames(const ULane *__restrict__ lanes, const KfArgs *__restrict__ A, int32_t
      * kernel whose instruction cache holds 64 KB) */
     const int32_t mode = J.mode;
     const int32_t gtid = r * KF_NT + tid, gstride = C * KF_NT;
-    bool resumed = J.resume != 0, handed = false, all_scored = false;
+    bool resumed = J.resume != 0 || mid_left, handed = false, all_scored = false;
     if (resumed && C > 1) {     /* (the lane's mask of a frame: clean between frames -- unless an utterance once stopped inside one) */
         if (r == 0) for (int32_t i = tid; i < KF_SENBITS / 32; i += KF_NT) L.senbits[i] = 0u;
         kf_barrier(B);
@@ -3003,6 +3018,7 @@ ku_frames(const ULane *__restrict__ lanes, const KfArgs *__restrict__ A, int32_t
                 }
                 else u_ = atomicAdd(J.next, 1);
                 sh.u = u_;
+                if (J.f_ready && (u_ >= J.n1 || all_scored)) sh.fk = INT32_MAX;     /* (not one of the first takes: its rows are whole before *q_ready says so) */
                 if (C > 1) __hip_atomic_store(&J.lane_u[z], u_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             kf_barrier(B);
@@ -3049,17 +3065,53 @@ ku_frames(const ULane *__restrict__ lanes, const KfArgs *__restrict__ A, int32_t
         for (int32_t f = f_lo; f < f_hi; f++) {
             /* (the word level ends an utterance that ran into an error: uniform over the cluster behind the frame's last barrier) */
             if (!((volatile UCtx *)ctx)->active || sh.dead) break;
-            if (J.stop_at > 0) {
+            /* ROWS AHEAD (J.f_ready; one workgroup per lane): a lane on one of the first takes reads row r0 + f only if f < *f_ready.  What it
+             * knows is in LDS; only at a frame at or beyond that does the thread that reads the relay's stop flag load the word again, on the
+             * way to the same barrier -- with the scoring ahead, every few dozen frames.  Still not scored: the lane LEAVES here. */
+            const bool ask = f >= sh.fk;
+            if (J.stop_at > 0 || ask) {
                 /* the relay's stop flag, as ONE thread of the lane read it (a cluster's workgroups must leave at the same frame) */
                 if (r == 0 && tid == 0) {
-                    const int32_t st = __hip_atomic_load(&J.st_cur[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const int32_t st = J.stop_at > 0 ? __hip_atomic_load(&J.st_cur[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
                     sh.u2 = st;
                     if (C > 1) __hip_atomic_store(&J.lane_stop[z], st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (ask) sh.fk2 = __hip_atomic_load(J.f_ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 kf_barrier(B);
                 if (C > 1 && r > 0 && tid == 0) sh.u2 = __hip_atomic_load(&J.lane_stop[z], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (C > 1) __syncthreads();
-                if (sh.u2) {
+                const int32_t stop = sh.u2;
+                if (ask) {
+                    const int32_t F = sh.fk2;
+                    /* (the rows below F were written by kernels that ended before the word said so: what was read acquires them) */
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                    if (tid == 0) sh.fk = F;            /* (read again at the next frame, behind this frame's barriers) */
+                    if (f >= F) {
+                        /* as a lane that leaves between two utterances, but with the frame it goes on with: everything frame f needs of
+                         * frame f - 1 is in device memory (the relay's hand-over rests on the same) */
+                        if (tid == 0) { sh.kacc[12] += (long long)wall_clock64() - t_launch; sh.kacc[14]++; J.lane_f[z] = f; }
+                        __syncthreads();
+                        if (tid < 16) { ctx->kacc[tid] += sh.kacc[tid]; sh.kacc[tid] = 0; }
+                        if (tid == 0 && J.ov == 1) {
+                            ctx->kdbg[0] = t_launch; ctx->kdbg[1] = (long long)wall_clock64();
+                            ctx->kdbg[2] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4); ctx->kdbg[3] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 20);
+                        }
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        __syncthreads();
+                        if (tid == 0) {
+                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                            sh.u2 = atomicCAS(&J.lane_left[z], 0, 3);
+                        }
+                        __syncthreads();
+                        if (sh.u2 == 0) return;
+                        /* (the second launch's workgroup has come and gone: it runs behind ALL the scoring, so the frame is scored after all) */
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                        if (tid == 0) sh.fk = INT32_MAX;
+                        all_scored = true;
+                        t_launch = (long long)wall_clock64();
+                    }
+                }
+                if (stop) {
                     if (r == 0 && tid == 0) {
                         J.lane_f[z] = f;
                         J.st_next[KF_ST_WORDS + atomicAdd(&J.st_next[2], 1)] = z;
@@ -3494,10 +3546,10 @@ struct s3a_uttdec_s {
     double kf_score_ms, kf_frames_ms;
     /* scoring beside the search (kf_decode_queue): the second stream and the events that order the two, the lanes' flags, the last call's figures */
     hipStream_t kf_stream2;
-    hipEvent_t kf_ov_ev[2];     /* the first utterances scored | the second stream's launch through */
-    int32_t *d_kfleft;          /* [n_lanes] a lane left for want of scores */
+    hipEvent_t kf_ov_ev[3];     /* the first utterances' lead scored | the second stream's launch through | ku_frames #1 through (kf_overlap_hold) */
+    int32_t *d_kfleft;          /* [3 n_lanes] a lane left for want of scores | the frame | the utterance it left in, for a call without the relay's arrays */
     int32_t kf_overlapped;      /* the last call ran that plan */
-    int32_t kf_n_resumed;       /* ... lanes that left and were resumed */
+    int32_t kf_lead;            /* ... frames of every first utterance scored before the search began (0: all) */
     int32_t kf_comp_lds;        /* dynamic LDS a companion scoring workgroup may take beside one ku_frames workgroup (0: not asked yet) */
 };
 
@@ -3873,7 +3925,7 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
         DM(ud->mem, ud->d_kfbar, (size_t)n_lanes * 8);
         if (hipMemset(ud->d_kfbar, 0, (size_t)n_lanes * 8) != hipSuccess) goto fail;
         DM(ud->mem, ud->d_kfrelay, ((size_t)(KF_STAGES + 1) * (KF_ST_WORDS + n_lanes) + (size_t)3 * n_lanes) * 4);
-        DM(ud->mem, ud->d_kfleft, (size_t)n_lanes * 4);
+        DM(ud->mem, ud->d_kfleft, (size_t)3 * n_lanes * 4);
         if (ud->device >= 0 && ud->device < 64) { g_kf_live[ud->device]++; ud->kf_counted = 1; ud->kf_shared = kf_device_lock(ud->device) ? 0 : 1; }
     }
     ud->scan_small_from = O.scan_small_from > 0 ? O.scan_small_from : 64;
@@ -4436,20 +4488,29 @@ kf_launch(s3a_uttdec_t *ud, int32_t n, const KfJob &J)
  * at their next frame boundary and the next launch -- enqueued here, up front, behind the first -- continues them that way.  A launch of
  * the chain that is handed nothing ends at once.  Only an engine that may size clusters for the whole device plans a chain (kf_alone; not
  * with s3a_uttdec_opts_t.cluster set: the caller's cluster size holds for the whole call); s3a_variants_t.kf_no_relay: never. */
-/* SCORING BESIDE THE SEARCH: the chain's first launch as three, over two streams (KfOverlap: kf_decode_queue, which has scored the first
- * n1 takes' utterances on the engine's stream and set *q_ready = n1).
+/* SCORING BESIDE THE SEARCH: the chain's first launch as three, over two streams (KfOverlap: kf_decode_queue, which has scored the LEAD -- the
+ * first frames of each of the first n1 takes' utterances -- on the engine's stream and set *q_ready = n1, *f_ready = the lead).
  *   engine stream   ku_frames #1: lanes 0 .. n1 - 1, one workgroup each -- half a CU each (NOT one per CU: of the bench's 256 CUs 87 were
  *                   seen with two of the 256 lanes, 82 with one, 87 with none; the companion's workgroups take whatever halves are free,
  *                   two of them fit a CU as well);
- *   second stream   behind the first utterances' scoring: the COMPANION scoring of groups [g0, g0 + n_g) in the CUs' other halves, then
- *                   *q_ready = n_utt, then ku_frames #2 over ALL n lanes: lanes n1 .. n - 1 start; of lanes 0 .. n1 - 1 one that LEFT #1
- *                   because its next take was not scored yet goes on taking, and the workgroup of one still at work in #1 (it will find
- *                   everything scored) ends at once.  (A launch on the engine's stream behind #1 would hold the lanes that left until #1's
- *                   LAST lane is through -- the end of the queue: measured, profiles/r7_overlap_experiments.txt.)
+ *   second stream   behind the lead's scoring, all of it the COMPANION's, in the CUs' other halves: first the ROUNDS of the first n1
+ *                   utterances -- a round is the next R groups of each of them, one launch, and a 4-byte fill behind it moves *f_ready on
+ *                   (INT32_MAX behind the last) --, then the other utterances' groups [g0, g0 + n_g) in take order with *q_ready
+ *                   following launch by launch, then ku_frames #2 over ALL n lanes: lanes n1 .. n - 1 start; of lanes 0 .. n1 - 1 one that
+ *                   LEFT #1 -- between two utterances because its next take was not scored yet, or inside one because its next frame was
+ *                   not -- goes on where it left, and the workgroup of one still at work in #1 (it will find everything scored) ends at
+ *                   once.  (A launch on the engine's stream behind #1 would hold the lanes that left until #1's LAST lane is through --
+ *                   the end of the queue: measured, profiles/r7_overlap_experiments.txt.)
  * The engine's stream then waits for the second one: what follows (the relay's launches, the call's close) is behind both.  Nothing on the
  * device waits for another kernel: the order is the streams' and the events', and a lane changes hands by one compare-and-swap on its flag
- * (KfJob.lane_left). */
-struct KfOverlap { int32_t n1; size_t g0, n_g; const size_t *g_end; };      /* (g_end[k]: the groups up to and with the k-th take's utterance) */
+ * (KfJob.lane_left).  n_rd = 0 (s3a_variants_t.kf_overlap_whole): the first n1 utterances were scored WHOLE up front, no *f_ready.
+ * hold (s3a_variants_t.kf_overlap_hold): every fill of the second stream and #2 wait for the END of #1 -- what happens by itself where
+ * dispatches do not overlap (under a profiler): every first lane runs to its lead, or to the end of a shorter utterance, and leaves. */
+struct KfOverlap {
+    int32_t n1; size_t g0, n_g; const size_t *g_end;        /* (g_end[k]: the groups up to and with the k-th take's utterance) */
+    int32_t n_rd, n_lead, hold;                             /* rounds of the first n1 utterances' groups; those scored up front */
+    const size_t *rd_g; const int32_t *rd_f;                /* [n_rd + 1] a round's first group in the table | [n_rd] the frames scored behind it */
+};
 #define SB_PIECE 1024
 static void kf_mark(s3a_uttdec_t *ud, hipStream_t st);
 static int32_t
@@ -4457,12 +4518,27 @@ kf_launch_overlapped(s3a_uttdec_t *ud, int32_t n, KfJob J, const KfOverlap &ov)
 {
     hipStream_t s1 = ud->stream, s2 = ud->kf_stream2;
     int32_t rc;
-    J.q_ready = ud->d_kfnext + 1; J.n_resumed = ud->d_kfnext + 2; J.lane_left = ud->d_kfleft;
+    int32_t *const q_ready = ud->d_kfnext + 1, *const f_ready = ud->d_kfnext + 3;
+    J.q_ready = q_ready; J.n_resumed = ud->d_kfnext + 2; J.n_inside = ud->d_kfnext + 4; J.lane_left = ud->d_kfleft;
     J.n1 = ov.n1;
+    if (ov.n_rd > 0) {
+        J.f_ready = f_ready;
+        /* (where a lane that leaves inside an utterance says so: the relay's arrays when the call has them -- a lane is in one launch's
+         * hands at a time, and the relay's launches are behind #2 --, else the engine's own) */
+        if (!J.lane_f) { J.lane_f = ud->d_kfleft + ud->n_lanes; J.lane_uq = J.lane_f + ud->n_lanes; }
+    }
     HIPCHK(hipEventRecord(ud->kf_ov_ev[0], s1));
     J.ov = 1;
     if ((rc = kf_launch_c(ud, ov.n1, J, 1, s1)) != S3A_OK) return rc;
+    if (ov.hold) HIPCHK(hipEventRecord(ud->kf_ov_ev[2], s1));
     HIPCHK(hipStreamWaitEvent(s2, ud->kf_ov_ev[0], 0));
+    for (int32_t k = ov.n_lead; k < ov.n_rd; k++) {
+        for (size_t g = ov.rd_g[k]; g < ov.rd_g[k + 1]; g += SB_PIECE) {
+            if ((rc = uw_launch(ud, 0, 0, false, ud->sb_gdesc.d + g, (int32_t)min((size_t)SB_PIECE, ov.rd_g[k + 1] - g), true, s2)) != S3A_OK) return rc;
+            ud->kf_n_score++;
+        }
+        if (!ov.hold) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)f_ready, k + 1 < ov.n_rd ? ov.rd_f[k] : INT32_MAX, 1, s2));
+    }
     /* (*q_ready follows the scoring launch by launch: the groups are in the order of the takes, and the companion scores utterances faster
      * than the first lanes decode them -- a lane of #1 that is through with its utterance finds the next ones scored and stays; with one
      * step to n_utt at the end 239 of 256 lanes left and idled until then, profiles/r7_overlap_experiments.txt) */
@@ -4473,10 +4549,15 @@ kf_launch_overlapped(s3a_uttdec_t *ud, int32_t n, KfJob J, const KfOverlap &ov)
         ud->kf_n_score++;
         const int32_t was = ready;
         while (ready < J.n_utt && ov.g_end[ready] <= ov.g0 + g + m) ready++;
-        if (ready > was) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(ud->d_kfnext + 1), ready, 1, s2));
+        if (ready > was && !ov.hold) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)q_ready, ready, 1, s2));
     }
     kf_mark(ud, s2);                                    /* (the last scoring launch's end: kf_collect) */
-    if (ready < J.n_utt) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(ud->d_kfnext + 1), J.n_utt, 1, s2));
+    if (ov.hold) {
+        HIPCHK(hipStreamWaitEvent(s2, ud->kf_ov_ev[2], 0));
+        if (ov.n_lead < ov.n_rd) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)f_ready, INT32_MAX, 1, s2));
+        ready = ov.n1;
+    }
+    if (ready < J.n_utt) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)q_ready, J.n_utt, 1, s2));
     J.ov = 2;
     if ((rc = kf_launch_c(ud, n, J, 1, s2)) != S3A_OK) return rc;
     HIPCHK(hipEventRecord(ud->kf_ov_ev[1], s2));
@@ -4618,6 +4699,45 @@ sb_describe(s3a_uttdec_t *ud, const float *const *feat_dev, const int32_t *n_fra
     return g - g_at;
 }
 
+/* ... of the first n1 takes' utterances in ROUNDS (kf_launch_overlapped): the same rows as sb_describe's -- row0[u] + f, in take order --, but
+ * the groups' ORDER is round by round: the first lead_g groups of each utterance, then the next R of each, and so on; an utterance that has
+ * ended is skipped.  rd_g: where each round begins in the table (and the last one ends); rd_f: the frames [0, min(rd_f, n_frames)) of EVERY
+ * one of these utterances are scored once that round is.  Returns the groups written. */
+static size_t
+sb_describe_rounds(s3a_uttdec_t *ud, const float *const *feat_dev, const int32_t *n_frames, int32_t n1, const int32_t *order, int32_t lead_g, int32_t R,
+                   std::vector<size_t> &rd_g, std::vector<int32_t> &rd_f)
+{
+    const size_t S_ = (size_t)ud->S.n_sen;
+    const int32_t DP = ud->S.D4 * 4;
+    size_t row = 0, g = 0;
+    long long max_g = 0;
+    for (int32_t k = 0; k < n1; k++) {
+        const int32_t u = order[k];
+        ud->sb_row0.h[u] = (long long)row;
+        row += (size_t)n_frames[u];
+        max_g = max(max_g, (long long)(n_frames[u] + UW_FB - 1) / UW_FB);
+    }
+    rd_g.assign(1, 0); rd_f.clear();
+    for (long long a = 0; a < max_g; ) {
+        const long long b = min(max_g, a + (a == 0 ? lead_g : R));
+        for (int32_t k = 0; k < n1; k++) {
+            const int32_t u = order[k];
+            const size_t r0 = (size_t)ud->sb_row0.h[u];
+            for (long long j = a; j < b && j * UW_FB < n_frames[u]; j++, g++) {
+                const int32_t j0 = (int32_t)j * UW_FB;
+                UwGroup &gr = ud->sb_gdesc.h[g];
+                gr.feat = feat_dev[u] + (size_t)j0 * DP;
+                gr.win = ud->sb_scores.d + (r0 + j0) * S_;
+                gr.winb = ud->sb_bests.d + (r0 + j0) * S_;
+                gr.nv = min(UW_FB, n_frames[u] - j0); gr.pad = 0;
+            }
+        }
+        rd_g.push_back(g); rd_f.push_back((int32_t)(b * UW_FB));
+        a = b;
+    }
+    return g;
+}
+
 /* score the groups [g0, g0 + n_g) of the uploaded table: launches of up to SB_PIECE groups */
 static int32_t
 sb_score(s3a_uttdec_t *ud, size_t g0, size_t n_g, bool companion = false, hipStream_t st = NULL)
@@ -4696,8 +4816,10 @@ kf_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat_dev, c
         if (!s3a_variants()->kf_queue_in_order)
             std::stable_sort(ud->kf_order.h + cut[k], ud->kf_order.h + cut[k + 1], [&](int32_t a, int32_t b) { return n_frames[a] > n_frames[b]; });
     }
-    /* SCORING BESIDE THE SEARCH (kf_launch_overlapped): only the first n1 takes' utterances are scored up front; the rest is scored by the
-     * companion shape in the halves of the CUs that n1 lanes leave free, and the other lanes start when it is through.  Only where the plan's
+    /* SCORING BESIDE THE SEARCH (kf_launch_overlapped): only a LEAD of the first n1 takes' utterances -- their first kf_overlap_lead frames --
+     * is scored up front; the rest is scored by the companion shape in the halves of the CUs that n1 lanes leave free: first those utterances'
+     * later frames in rounds of R groups each, with *f_ready saying how far all of them are scored, then the other utterances; the other lanes
+     * start when it is through.  (kf_overlap_whole: the first n1 utterances WHOLE up front, as before the rounds.)  Only where the plan's
      * premise holds -- an engine that sizes its launches for the whole device (as the relay), two lanes per CU, more utterances than lanes --
      * and only for the plain call: one part, no second pass, no look-ahead heuristic, no kept lattices.  s3a_variants_t: kf_overlap = 1
      * asks for it (KF_OVERLAP_DEFAULT: without being asked), kf_overlap_n1 > 0 forces it with that many first lanes (the tests' small
@@ -4717,10 +4839,18 @@ kf_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat_dev, c
             if (n1 > 0 && !e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); e = NULL; n1 = 0; }
     }
     ud->kf_overlapped = n1 > 0 ? 1 : 0;
-    std::vector<size_t> g_at(cut.size(), 0), g_end;
+    ud->kf_lead = 0;
+    std::vector<size_t> g_at(cut.size(), 0), g_end, rd_g;
+    std::vector<int32_t> rd_f;
     size_t g_first = 0;             /* (the plan: the groups of the first n1 takes' utterances) */
     if (n1 > 0) {
-        g_first = sb_describe(ud, feat_dev, n_frames, 0, n1, 0, ud->kf_order.h);
+        if (va->kf_overlap_whole) g_first = sb_describe(ud, feat_dev, n_frames, 0, n1, 0, ud->kf_order.h);
+        else {
+            const int32_t lead_g = (max(0, va->kf_overlap_lead) + UW_FB - 1) / UW_FB;
+            g_first = sb_describe_rounds(ud, feat_dev, n_frames, n1, ud->kf_order.h, lead_g > 0 ? lead_g : KF_OVERLAP_LEAD / UW_FB,
+                                         va->kf_overlap_round > 0 ? va->kf_overlap_round : max(1, SB_PIECE / n1), rd_g, rd_f);
+            if (!rd_f.empty()) ud->kf_lead = rd_f[0];
+        }
         /* (one run of rows over both pieces: the second piece's rows go on where the first one's end) */
         const size_t rows1 = (size_t)ud->sb_row0.h[ud->kf_order.h[n1 - 1]] + (size_t)n_frames[ud->kf_order.h[n1 - 1]];
         g_at[1] = g_first + sb_describe(ud, feat_dev, n_frames, n1, n_utt, g_first, ud->kf_order.h);
@@ -4746,11 +4876,15 @@ kf_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat_dev, c
     for (size_t k = 0; k + 1 < cut.size(); k++) {
         const int32_t u0 = cut[k], nu = cut[k + 1] - cut[k];
         kf_mark(ud);
-        if ((rc = sb_score(ud, g_at[k], n1 > 0 ? g_first : g_at[k + 1] - g_at[k])) != S3A_OK) return rc;
+        /* (the lead through the companion shape: alone it is the faster of the two, profiles/r7_overlap_experiments.txt 0) */
+        if (n1 > 0 && !rd_f.empty()) rc = sb_score(ud, 0, rd_g[1], true);
+        else rc = sb_score(ud, g_at[k], n1 > 0 ? g_first : g_at[k + 1] - g_at[k]);
+        if (rc != S3A_OK) return rc;
         kf_mark(ud);
-        if (n1 > 0) {               /* (the counter, *q_ready = n1, the resumed lanes' count; no lane has left) */
+        if (n1 > 0) {               /* (the counter, *q_ready = n1, the resumed lanes' counts, *f_ready = the lead; no lane has left) */
             HIPCHK(hipMemsetAsync(ud->d_kfnext, 0, 16 * 4, ud->stream));
             HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(ud->d_kfnext + 1), n1, 1, ud->stream));
+            if (!rd_f.empty()) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(ud->d_kfnext + 3), rd_f.size() > 1 ? rd_f[0] : INT32_MAX, 1, ud->stream));
             HIPCHK(hipMemsetAsync(ud->d_kfleft, 0, (size_t)ud->n_lanes * 4, ud->stream));
         }
         else HIPCHK(hipMemsetAsync(ud->d_kfnext, 0, 4, ud->stream));
@@ -4759,7 +4893,7 @@ kf_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat_dev, c
         J.mode = KF_QUEUE; J.n_utt = nu; J.u0 = u0; J.order = ud->kf_order.d; J.next = ud->d_kfnext; J.lane_u = ud->d_kfnext + 16; J.stage = ud->q_ctx.d;
         J.row0 = ud->sb_row0.d; J.scores = ud->sb_scores.d; J.bests = ud->sb_bests.d;
         J.hdr = ud->q_hdr.d; J.words = ud->q_words.d; J.wcount = wcount; J.P = P; J.B = B; J.n_word = ud->cfg.n_word;
-        const KfOverlap ov = { n1, g_first, g_at[1] - g_first, g_end.data() };
+        const KfOverlap ov = { n1, g_first, g_at[1] - g_first, g_end.data(), (int32_t)rd_f.size(), 1, va->kf_overlap_hold != 0, rd_g.data(), rd_f.data() };
         if ((rc = kf_launch_chain(ud, min(ud->n_lanes, nu), J, n1 > 0 ? &ov : NULL)) != S3A_OK) return rc;
         ud->kf_n_frames++;
         kf_mark(ud);
@@ -5450,6 +5584,21 @@ s3a_uttdec_last_overlap(s3a_uttdec_t *ud, int32_t *overlapped, int32_t *resumed)
         if (ud->kf_overlapped) {
             HIPCHK(hipSetDevice(ud->device));
             HIPCHK(hipMemcpy(resumed, ud->d_kfnext + 2, 4, hipMemcpyDeviceToHost));
+        }
+    }
+    return S3A_OK;
+}
+
+extern "C" int32_t
+s3a_uttdec_last_overlap2(s3a_uttdec_t *ud, int32_t *left_inside, int32_t *lead)
+{
+    if (!ud) return S3A_EINVAL;
+    if (lead) *lead = ud->kf_overlapped ? ud->kf_lead : 0;
+    if (left_inside) {
+        *left_inside = 0;
+        if (ud->kf_overlapped) {
+            HIPCHK(hipSetDevice(ud->device));
+            HIPCHK(hipMemcpy(left_inside, ud->d_kfnext + 4, 4, hipMemcpyDeviceToHost));
         }
     }
     return S3A_OK;

@@ -213,6 +213,7 @@ _SIGS = {
     "s3a_uttdec_last_parts": (C.c_int32, [C.c_void_p] + [C.c_void_p] * 5),
     "s3a_uttdec_last_relay": (C.c_int32, [C.c_void_p]),
     "s3a_uttdec_last_overlap": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3a_uttdec_last_overlap2": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "s3a_uttdec_queue_keep_lattices": (C.c_int32, [C.c_void_p, C.c_int32]),
     "s3a_uttdec_queue_lattice": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "s3a_uttdec_n_lanes": (C.c_int32, [C.c_void_p]),
@@ -1395,7 +1396,8 @@ class Variants(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("scan_chained", "calls_by_copy", "batch_no_shared", "batch_no_multi",
                                          "no_frame_sync_kernel", "score_nt", "score_fpc", "resolve_sweep", "hist_sort_launch", "ps_overlap", "ps_score_by_gaussian",
                                          "kf_queue_in_order", "kf_no_relay", "kf_relay_at",
-                                         "kf_no_overlap", "kf_overlap", "kf_overlap_n1", "uw_companion")]
+                                         "kf_no_overlap", "kf_overlap", "kf_overlap_n1", "uw_companion",
+                                         "kf_overlap_lead", "kf_overlap_round", "kf_overlap_whole", "kf_overlap_hold")]
 
 
 def set_variants(**kw):
@@ -1609,6 +1611,13 @@ class UttDec:
         o, r = C.c_int32(), C.c_int32()
         check(self.L.s3a_uttdec_last_overlap(self.h, C.byref(o), C.byref(r)), self.L)
         return dict(overlapped=o.value, resumed=r.value)
+
+    def last_overlap2(self):
+        """-> dict(left_inside, lead) of the last decode: those of the resumed lanes that left INSIDE an utterance, at a frame that was not
+        scored yet; the frames of each first utterance scored before the search began (s3a_uttdec_last_overlap2)"""
+        n, l = C.c_int32(), C.c_int32()
+        check(self.L.s3a_uttdec_last_overlap2(self.h, C.byref(n), C.byref(l)), self.L)
+        return dict(left_inside=n.value, lead=l.value)
 
     def last_relay(self):
         """launches the last call's relay had behind its first (s3a_uttdec_last_relay)"""

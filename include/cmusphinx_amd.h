@@ -813,9 +813,13 @@ int32_t s3a_uttdec_wl_ticks(s3a_uttdec_t *ud, int32_t lane, long long *out16);
 int32_t s3a_uttdec_last_parts(s3a_uttdec_t *ud, double *score_ms, int32_t *n_score, double *frames_ms, int32_t *n_frames, int32_t *cluster);
 /* ... a queue that was scored BESIDE the search (s3a_variants_t.kf_overlap ...): *overlapped = 1, and then score_ms spans the first scoring
  * launch's start to the last one's end, frames_ms the first ku_frames launch's start to the last one's end -- the two spans OVERLAP, their
- * sum is more than the call took.  *resumed: lanes that found their next utterance not scored yet, left their launch and were taken up again
- * by the launch behind the scoring. */
+ * sum is more than the call took.  *resumed: lanes that found their next utterance (or, s3a_uttdec_last_overlap2, their next frame) not scored
+ * yet, left their launch and were taken up again by the launch behind the scoring. */
 int32_t s3a_uttdec_last_overlap(s3a_uttdec_t *ud, int32_t *overlapped, int32_t *resumed);
+/* ... *left_inside: those of the resumed lanes that left INSIDE an utterance, at a frame whose scores were not written yet
+ * (s3a_variants_t.kf_overlap_lead ...); *lead: the frames of each of the first lanes' utterances that were scored before the search began
+ * (0: the call did not run the plan, or scored them whole). */
+int32_t s3a_uttdec_last_overlap2(s3a_uttdec_t *ud, int32_t *left_inside, int32_t *lead);
 int32_t s3a_uttdec_frame_ticks(s3a_uttdec_t *ud, int32_t lane, long long *out16, int32_t *cluster);
 /* diagnostics: launches the last call's RELAY had behind its first (0: one launch to the end).  A ku_frames call ends with its slowest
  * lane; when no utterance is left to take and few lanes are still at work, they hand over at a frame boundary to a launch that continues
@@ -1258,6 +1262,15 @@ typedef struct {
                                      * tests use it with a handful of lanes; the call's own conditions still hold) */
     int32_t uw_companion;           /* the up-front scoring passes of ku_frames' calls through the companion shape (256 threads, the LDS a CU has left
                                      * beside a ku_frames workgroup): the same rows, for tests without any concurrency */
+    /* ... ROWS AHEAD: of the first lanes' utterances only a LEAD is scored before the search begins; their later frames are scored beside it in
+     * rounds, a few groups of 8 frames of each utterance per launch, and a device word says how far all of them are scored.  A lane that reaches
+     * a frame beyond it leaves at that frame boundary and the launch behind the scoring continues the utterance there. */
+    int32_t kf_overlap_lead;        /* the lead in frames, a multiple of 8 (0: the library's, profiles/r8_rows_ahead_experiments.txt) */
+    int32_t kf_overlap_round;       /* groups of each utterance per round (0: as many as make a launch of 1024 groups; tests' small engines use 1) */
+    int32_t kf_overlap_whole;       /* the first lanes' utterances scored WHOLE before the search begins, as before the rounds (A/B) */
+    int32_t kf_overlap_hold;        /* everything the second stream tells the lanes, and the launch behind the scoring, waits for the END of the first
+                                     * launch: what happens by itself where dispatches do not overlap (under a profiler), made deterministic for
+                                     * tests -- every first lane runs to its lead, or to the end of a shorter utterance, and leaves */
 } s3a_variants_t;
 void    s3a_variants_default(s3a_variants_t *v);
 void    s3a_get_variants(s3a_variants_t *v);            /* the variants in force (read-modify-write with s3a_set_variants) */

@@ -93,7 +93,7 @@ def main():
         rows = [decs[0].ud.frame_dbg(z) for z in range(NLE)]
         t0 = min(r[0] for r in rows)
         n1 = NLE // 2
-        out = {"device_ms": round(ms, 1), "parts": decs[0].ud.last_parts(), "overlap": decs[0].ud.last_overlap(), "relay": decs[0].ud.last_relay()}
+        out = {"device_ms": round(ms, 1), "parts": decs[0].ud.last_parts(), "overlap": decs[0].ud.last_overlap(), "rows_ahead": decs[0].ud.last_overlap2(), "relay": decs[0].ud.last_relay()}
         for name, zs in (("first_launch", range(n1)), ("second_launch", range(n1, NLE))):
             cus = {}
             for z in zs:
