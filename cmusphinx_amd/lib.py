@@ -19,6 +19,7 @@ S3A_OK = 0
 LOGPROB_ZERO = -939524096
 GMM_EXACT, GMM_FAST = 0, 1
 MIX_INT_FLOAT_COMP = 2
+MS_RAW = 1              # S3A_MS_RAW
 
 # every symbol include/cmusphinx_amd.h declares (checked by tests/test_abi.py)
 _SIGS = {
@@ -152,6 +153,11 @@ _SIGS = {
     "s3a_ms_mgau_veclen": (C.c_int32, [C.c_void_p]),
     "s3a_ms_cont_mgau_frame_eval": (C.c_int32, [C.c_void_p] * 4 + [C.c_int32, C.POINTER(C.c_int32)]),
     "s3a_ms_mgau_get_dist": (C.c_int32, [C.c_void_p] * 3),
+    "s3a_ms_mgau_score_frames": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_int32]),
+    "s3a_ms_mgau_score_frames_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "s3a_ms_mgau_set_block_chunk": (C.c_int32, [C.c_void_p, C.c_int32]),
     "s3a_batch_create": (C.c_void_p, [C.c_int32]),
     "s3a_batch_free": (None, [C.c_void_p]),
     "s3a_batch_attach": (C.c_int32, [C.c_void_p] * 4),
@@ -817,6 +823,34 @@ class MsMgau:
         best = C.c_int32(0)
         check(self.L.s3a_ms_cont_mgau_frame_eval(self.h, _p(sa), _p(senscr), _p(x), int(frame), C.byref(best)))
         return best.value
+
+    def score_frames(self, feat, sen_active=None, raw=False, senscr=None):
+        """ms_cont_mgau_frame_eval for all the frames of feat [T][veclen] in one call -> (senscr [T][S], best [T]).
+        sen_active: uint8 [T][S] or None (all active); raw: rows not normalised (S3A_MS_RAW); senscr: rows to
+        update in place (only the active entries are written) instead of fresh zeros."""
+        x = np.ascontiguousarray(feat, np.float32).reshape(-1, self.veclen)
+        T = x.shape[0]
+        sa = None if sen_active is None else np.ascontiguousarray(sen_active, np.uint8).reshape(T, self.n_sen)
+        if senscr is None:
+            senscr = np.zeros((T, self.n_sen), np.int32)
+        assert senscr.dtype == np.int32 and senscr.flags.c_contiguous and senscr.size == T * self.n_sen
+        best = np.zeros(T, np.int32)
+        check(self.L.s3a_ms_mgau_score_frames(self.h, _p(x), T, None if sa is None else _p(sa), _p(senscr), _p(best),
+                                              MS_RAW if raw else 0), self.L)
+        return senscr, best
+
+    def score_frames_dev(self, feat_dev: DevBuf, n_frames, scr_dev: DevBuf, sen_active_dev: DevBuf = None,
+                         best_dev: DevBuf = None, feat_stride=None, row_stride=None, raw=False, stream=None):
+        """The same on device buffers (DevBuf), asynchronous on `stream` (None: the model's own)."""
+        check(self.L.s3a_ms_mgau_score_frames_dev(
+            self.h, feat_dev.ptr, self.veclen if feat_stride is None else int(feat_stride), int(n_frames),
+            sen_active_dev.ptr if sen_active_dev else None, scr_dev.ptr,
+            self.n_sen if row_stride is None else int(row_stride), best_dev.ptr if best_dev else None,
+            MS_RAW if raw else 0, stream), self.L)
+
+    def set_block_chunk(self, n):
+        """Test hook: at most n frames per internal pass of score_frames* (0: the library's choice)."""
+        check(self.L.s3a_ms_mgau_set_block_chunk(self.h, int(n)), self.L)
 
     def last_dist(self):
         n = self.n_mgau * self.n_feat * self.topn

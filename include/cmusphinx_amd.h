@@ -387,6 +387,31 @@ int32_t s3a_ms_cont_mgau_frame_eval(s3a_ms_mgau_t *msg, const uint8_t *sen_activ
 /* the top-N lists of the last frame, [n_mgau][n_feat][topn] (test hook; inactive codebooks stale) */
 int32_t s3a_ms_mgau_get_dist(s3a_ms_mgau_t *msg, int32_t *dist, int32_t *dist_id);
 
+#define S3A_MS_RAW 1   /* flags: rows are NOT normalised (senscr[t][s] = senone_eval's value); best[t] is still reported */
+
+/* ms_cont_mgau_frame_eval (ms_mgau.c:242-329) for n_frames frames in one pass.
+ * feat        [n_frames][veclen]: each frame's streams concatenated
+ * sen_active  [n_frames][n_sen] uint8, or NULL = every senone active in every frame
+ * senscr      [n_frames][n_sen] int32; entries of senones inactive in their frame are left as the caller had them
+ * best        [n_frames] (may be NULL): the value the reference returns per frame (-> srch->senscale);
+ *             INT32_MIN for a frame with no active senone (the reference's 0x80000000), whose row is not written
+ * The same integers as n_frames calls of s3a_ms_cont_mgau_frame_eval.  Whether the codebooks of inactive senones
+ * are evaluated is not defined; s3a_ms_mgau_get_dist does not see these calls. */
+int32_t s3a_ms_mgau_score_frames(s3a_ms_mgau_t *msg, const float *feat, int32_t n_frames,
+                                 const uint8_t *sen_active, int32_t *senscr, int32_t *best, int32_t flags);
+
+/* The same with everything resident in HBM, asynchronous on `stream` (a hipStream_t as void *; NULL = the model's own).
+ * feat rows of feat_stride >= veclen floats; senscr rows of row_stride >= n_sen int32;
+ * sen_active_dev rows of n_sen bytes, or NULL; best_dev may be NULL.
+ * Internal scratch belongs to the model: one call at a time per handle. */
+int32_t s3a_ms_mgau_score_frames_dev(s3a_ms_mgau_t *msg, const float *feat_dev, int32_t feat_stride, int32_t n_frames,
+                                     const uint8_t *sen_active_dev, int32_t *senscr_dev, int32_t row_stride,
+                                     int32_t *best_dev, int32_t flags, void *stream);
+
+/* Test hook, as s3a_uttdec_opts_t.score_rows_max is: a cap on the frames one internal pass takes.
+ * 0 = the library's choice. Same bits either way. */
+int32_t s3a_ms_mgau_set_block_chunk(s3a_ms_mgau_t *msg, int32_t frames);
+
 /*
  * dict2pid_comsenscr (sphinx3/src/libs3decoder/libsearch/dict2pid.c:1029-1048):
  * comsenscr[i] = max_{k in comstate[i]} senscr[k] + comwt[i].  The ragged
