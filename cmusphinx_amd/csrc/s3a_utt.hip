@@ -45,6 +45,7 @@
 #include "s3a_lm3g.h"
 #include "s3a_dag.h"
 #include "s3a_hostmem.h"
+#include "s3a_kfplan.h"
 
 /* A pointer that came out of a structure in memory is a GENERIC pointer to the compiler; what it makes of an access through one is
  * flat_load / flat_store -- counted by the LDS counter as well as the memory counter, so that every wait for an LDS read waits for
@@ -3528,7 +3529,7 @@ struct s3a_uttdec_s {
     int32_t *d_kfbar;           /* [n_lanes][2] the clusters' barrier counters, the XCDs their workgroups run on (a bit each) */
     int32_t kf_last_c;          /* workgroups per lane of the last launch (diagnostics) */
     int32_t kf_counted;         /* this engine is counted in g_kf_live */
-    int32_t *d_kfnext;          /* [16 + n_lanes] the queue's counter | what a lane's first workgroup took */
+    int32_t *d_kfnext;          /* [KFN_LANE + n_lanes] the queue's words (KFN_*) | what a lane's first workgroup took */
     void *d_kfargs, *h_kfargs;  /* [KF_ARG_SLOTS] KfArgs: ku_frames' shared arguments (device / pinned) */
     int32_t kf_arg_at;
     /* SCORES FIRST: every frame's senone scores of a call (ku_frames, KF_STATIC / KF_QUEUE) */
@@ -3552,6 +3553,10 @@ struct s3a_uttdec_s {
     int32_t kf_lead;            /* ... frames of every first utterance scored before the search began (0: all) */
     int32_t kf_comp_lds;        /* dynamic LDS a companion scoring workgroup may take beside one ku_frames workgroup (0: not asked yet) */
 };
+
+/* the words of s3a_uttdec_s.d_kfnext (KF_QUEUE): the takes' counter; with scoring beside the search the takes scored (*q_ready), the lanes
+ * ku_frames #2 resumed, the frames of every first take scored (*f_ready), the lanes that left INSIDE an utterance; then a word per lane */
+enum { KFN_COUNTER = 0, KFN_Q_READY = 1, KFN_RESUMED = 2, KFN_F_READY = 3, KFN_INSIDE = 4, KFN_LANE = 16 };
 
 /* engines with ku_frames alive per device: an engine that is alone on its device may give a lane a cluster of workgroups */
 static std::atomic<int> g_kf_live[64];
@@ -3919,7 +3924,7 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
     ud->kf_cluster_opt = O.cluster;
     ud->sb_rows_max = O.score_rows_max > 0 ? (size_t)O.score_rows_max : 0;
     if (ud->persist) {
-        DM(ud->mem, ud->d_kfnext, (size_t)(16 + n_lanes) * 4);
+        DM(ud->mem, ud->d_kfnext, (size_t)(KFN_LANE + n_lanes) * 4);
         DM(ud->mem, ud->d_kfargs, sizeof(KfArgs) * KF_ARG_SLOTS);
         if (!ud->mem.pin(ud->h_kfargs, sizeof(KfArgs) * KF_ARG_SLOTS)) { s3a_set_error("s3a_uttdec_init: pinned allocation failed"); goto fail; }
         DM(ud->mem, ud->d_kfbar, (size_t)n_lanes * 8);
@@ -4488,7 +4493,7 @@ kf_launch(s3a_uttdec_t *ud, int32_t n, const KfJob &J)
  * at their next frame boundary and the next launch -- enqueued here, up front, behind the first -- continues them that way.  A launch of
  * the chain that is handed nothing ends at once.  Only an engine that may size clusters for the whole device plans a chain (kf_alone; not
  * with s3a_uttdec_opts_t.cluster set: the caller's cluster size holds for the whole call); s3a_variants_t.kf_no_relay: never. */
-/* SCORING BESIDE THE SEARCH: the chain's first launch as three, over two streams (KfOverlap: kf_decode_queue, which has scored the LEAD -- the
+/* SCORING BESIDE THE SEARCH: the chain's first launch as three, over two streams (a KfPlan with n1 > 0: kf_decode_queue, which has scored the LEAD -- the
  * first frames of each of the first n1 takes' utterances -- on the engine's stream and set *q_ready = n1, *f_ready = the lead).
  *   engine stream   ku_frames #1: lanes 0 .. n1 - 1, one workgroup each -- half a CU each (NOT one per CU: of the bench's 256 CUs 87 were
  *                   seen with two of the 256 lanes, 82 with one, 87 with none; the companion's workgroups take whatever halves are free,
@@ -4503,25 +4508,24 @@ kf_launch(s3a_uttdec_t *ud, int32_t n, const KfJob &J)
  *                   the end of the queue: measured, profiles/r7_overlap_experiments.txt.)
  * The engine's stream then waits for the second one: what follows (the relay's launches, the call's close) is behind both.  Nothing on the
  * device waits for another kernel: the order is the streams' and the events', and a lane changes hands by one compare-and-swap on its flag
- * (KfJob.lane_left).  n_rd = 0 (s3a_variants_t.kf_overlap_whole): the first n1 utterances were scored WHOLE up front, no *f_ready.
- * hold (s3a_variants_t.kf_overlap_hold): every fill of the second stream and #2 wait for the END of #1 -- what happens by itself where
- * dispatches do not overlap (under a profiler): every first lane runs to its lead, or to the end of a shorter utterance, and leaves. */
-struct KfOverlap {
-    int32_t n1; size_t g0, n_g; const size_t *g_end;        /* (g_end[k]: the groups up to and with the k-th take's utterance) */
-    int32_t n_rd, n_lead, hold;                             /* rounds of the first n1 utterances' groups; those scored up front */
-    const size_t *rd_g; const int32_t *rd_f;                /* [n_rd + 1] a round's first group in the table | [n_rd] the frames scored behind it */
-};
-#define SB_PIECE 1024
+ * (KfJob.lane_left).  P.lead = 0 (s3a_variants_t.kf_overlap_whole): the first n1 utterances were scored WHOLE up front, no *f_ready.
+ * What the second stream scores, and when *f_ready and *q_ready move on, is the plan's SCRIPT (s3a_kfplan.h); this function executes it.
+ * hold (s3a_variants_t.kf_overlap_hold): the same launches, but every fill of the second stream and #2 wait for the END of #1 -- what
+ * happens by itself where dispatches do not overlap (under a profiler): every first lane runs to its lead, or to the end of a shorter
+ * utterance, and leaves. */
+#define SB_PIECE KFP_PIECE
+static_assert(KFP_FB == UW_FB, "the plan's groups are the scoring kernel's");
 static void kf_mark(s3a_uttdec_t *ud, hipStream_t st);
 static int32_t
-kf_launch_overlapped(s3a_uttdec_t *ud, int32_t n, KfJob J, const KfOverlap &ov)
+kf_launch_overlapped(s3a_uttdec_t *ud, int32_t n, KfJob J, const KfPlan &P)
 {
     hipStream_t s1 = ud->stream, s2 = ud->kf_stream2;
+    const bool hold = s3a_variants()->kf_overlap_hold != 0;
     int32_t rc;
-    int32_t *const q_ready = ud->d_kfnext + 1, *const f_ready = ud->d_kfnext + 3;
-    J.q_ready = q_ready; J.n_resumed = ud->d_kfnext + 2; J.n_inside = ud->d_kfnext + 4; J.lane_left = ud->d_kfleft;
-    J.n1 = ov.n1;
-    if (ov.n_rd > 0) {
+    int32_t *const q_ready = ud->d_kfnext + KFN_Q_READY, *const f_ready = ud->d_kfnext + KFN_F_READY;
+    J.q_ready = q_ready; J.n_resumed = ud->d_kfnext + KFN_RESUMED; J.n_inside = ud->d_kfnext + KFN_INSIDE; J.lane_left = ud->d_kfleft;
+    J.n1 = P.n1;
+    if (P.lead > 0) {
         J.f_ready = f_ready;
         /* (where a lane that leaves inside an utterance says so: the relay's arrays when the call has them -- a lane is in one launch's
          * hands at a time, and the relay's launches are behind #2 --, else the engine's own) */
@@ -4529,35 +4533,25 @@ kf_launch_overlapped(s3a_uttdec_t *ud, int32_t n, KfJob J, const KfOverlap &ov)
     }
     HIPCHK(hipEventRecord(ud->kf_ov_ev[0], s1));
     J.ov = 1;
-    if ((rc = kf_launch_c(ud, ov.n1, J, 1, s1)) != S3A_OK) return rc;
-    if (ov.hold) HIPCHK(hipEventRecord(ud->kf_ov_ev[2], s1));
+    if ((rc = kf_launch_c(ud, P.n1, J, 1, s1)) != S3A_OK) return rc;
+    if (hold) HIPCHK(hipEventRecord(ud->kf_ov_ev[2], s1));
     HIPCHK(hipStreamWaitEvent(s2, ud->kf_ov_ev[0], 0));
-    for (int32_t k = ov.n_lead; k < ov.n_rd; k++) {
-        for (size_t g = ov.rd_g[k]; g < ov.rd_g[k + 1]; g += SB_PIECE) {
-            if ((rc = uw_launch(ud, 0, 0, false, ud->sb_gdesc.d + g, (int32_t)min((size_t)SB_PIECE, ov.rd_g[k + 1] - g), true, s2)) != S3A_OK) return rc;
+    size_t n_sc = P.script.size();                      /* (the steps up to and with the last scoring launch) */
+    while (n_sc > 0 && P.script[n_sc - 1].op != KFP_SCORE) n_sc--;
+    for (size_t i = 0; i < P.script.size(); i++) {
+        const KfStep &st = P.script[i];
+        if (st.op == KFP_SCORE) {
+            if ((rc = uw_launch(ud, 0, 0, false, ud->sb_gdesc.d + st.a, (int32_t)(st.b - st.a), true, s2)) != S3A_OK) return rc;
             ud->kf_n_score++;
         }
-        if (!ov.hold) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)f_ready, k + 1 < ov.n_rd ? ov.rd_f[k] : INT32_MAX, 1, s2));
+        else if (!hold) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(st.op == KFP_F_READY ? f_ready : q_ready), (int32_t)st.a, 1, s2));
+        if (i + 1 == n_sc) kf_mark(ud, s2);             /* (the last scoring launch's end: kf_collect) */
     }
-    /* (*q_ready follows the scoring launch by launch: the groups are in the order of the takes, and the companion scores utterances faster
-     * than the first lanes decode them -- a lane of #1 that is through with its utterance finds the next ones scored and stays; with one
-     * step to n_utt at the end 239 of 256 lanes left and idled until then, profiles/r7_overlap_experiments.txt) */
-    int32_t ready = ov.n1;
-    for (size_t g = 0; g < ov.n_g; g += SB_PIECE) {
-        const size_t m = min((size_t)SB_PIECE, ov.n_g - g);
-        if ((rc = uw_launch(ud, 0, 0, false, ud->sb_gdesc.d + ov.g0 + g, (int32_t)m, true, s2)) != S3A_OK) return rc;
-        ud->kf_n_score++;
-        const int32_t was = ready;
-        while (ready < J.n_utt && ov.g_end[ready] <= ov.g0 + g + m) ready++;
-        if (ready > was && !ov.hold) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)q_ready, ready, 1, s2));
-    }
-    kf_mark(ud, s2);                                    /* (the last scoring launch's end: kf_collect) */
-    if (ov.hold) {
+    if (hold) {
         HIPCHK(hipStreamWaitEvent(s2, ud->kf_ov_ev[2], 0));
-        if (ov.n_lead < ov.n_rd) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)f_ready, INT32_MAX, 1, s2));
-        ready = ov.n1;
+        if (P.f_ready0 > 0 && P.f_ready0 < INT32_MAX) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)f_ready, INT32_MAX, 1, s2));
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)q_ready, J.n_utt, 1, s2));
     }
-    if (ready < J.n_utt) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)q_ready, J.n_utt, 1, s2));
     J.ov = 2;
     if ((rc = kf_launch_c(ud, n, J, 1, s2)) != S3A_OK) return rc;
     HIPCHK(hipEventRecord(ud->kf_ov_ev[1], s2));
@@ -4566,7 +4560,7 @@ kf_launch_overlapped(s3a_uttdec_t *ud, int32_t n, KfJob J, const KfOverlap &ov)
 }
 
 static int32_t
-kf_launch_chain(s3a_uttdec_t *ud, int32_t n, KfJob J, const KfOverlap *ov = NULL)
+kf_launch_chain(s3a_uttdec_t *ud, int32_t n, KfJob J, const KfPlan *ov = NULL)
 {
     /* (kf_relay_at, the tests' switch: the chain from one workgroup per lane on, however few the lanes; scoring beside the search: one per lane) */
     const int32_t C0 = (s3a_variants()->kf_relay_at > 0 && ud->kf_cluster_opt == 0) || ov ? 1 : kf_choose_c(ud, n), usable = kf_usable_per_xcd(ud), W = KF_ST_WORDS + ud->n_lanes;
@@ -4676,66 +4670,27 @@ sb_reserve(s3a_uttdec_t *ud, size_t rows, size_t groups, size_t n_utt)
     return S3A_OK;
 }
 
-/* the groups of utterances [u0, u1): 8 consecutive frames each, rows from `row` on; returns the groups written
- * (order: the utterances order[u0 .. u1) in that order -- rows and groups then follow the order of the takes) */
-static size_t
-sb_describe(s3a_uttdec_t *ud, const float *const *feat_dev, const int32_t *n_frames, int32_t u0, int32_t u1, size_t g_at, const int32_t *order = NULL)
+/* a call's plan (s3a_kfplan.h) onto the device: the score buffer for its largest part, its groups as the scoring kernel's records (feat_dev[u]:
+ * utterance u's features on the device), its rows (P.row0's indexing) */
+static int32_t
+sb_load(s3a_uttdec_t *ud, const KfPlan &P, const float *const *feat_dev)
 {
-    const size_t S_ = (size_t)ud->S.n_sen;
+    const size_t S_ = (size_t)ud->S.n_sen, n_utt = P.order.size();
     const int32_t DP = ud->S.D4 * 4;
-    size_t row = 0, g = g_at;
-    for (int32_t k = u0; k < u1; k++) {
-        const int32_t u = order ? order[k] : k;
-        ud->sb_row0.h[u] = (long long)row;
-        for (int32_t j0 = 0; j0 < n_frames[u]; j0 += UW_FB, g++) {
-            UwGroup &gr = ud->sb_gdesc.h[g];
-            gr.feat = feat_dev[u] + (size_t)j0 * DP;
-            gr.win = ud->sb_scores.d + (row + j0) * S_;
-            gr.winb = ud->sb_bests.d + (row + j0) * S_;
-            gr.nv = min(UW_FB, n_frames[u] - j0); gr.pad = 0;
-        }
-        row += (size_t)n_frames[u];
+    int32_t rc;
+    if ((rc = sb_reserve(ud, P.max_rows, P.groups.size(), n_utt)) != S3A_OK) return rc;
+    for (size_t g = 0; g < P.groups.size(); g++) {
+        const KfGroup &k = P.groups[g];
+        UwGroup &gr = ud->sb_gdesc.h[g];
+        gr.feat = feat_dev[k.utt] + (size_t)k.first * DP;
+        gr.win = ud->sb_scores.d + (size_t)k.row * S_;
+        gr.winb = ud->sb_bests.d + (size_t)k.row * S_;
+        gr.nv = k.frames; gr.pad = 0;
     }
-    return g - g_at;
-}
-
-/* ... of the first n1 takes' utterances in ROUNDS (kf_launch_overlapped): the same rows as sb_describe's -- row0[u] + f, in take order --, but
- * the groups' ORDER is round by round: the first lead_g groups of each utterance, then the next R of each, and so on; an utterance that has
- * ended is skipped.  rd_g: where each round begins in the table (and the last one ends); rd_f: the frames [0, min(rd_f, n_frames)) of EVERY
- * one of these utterances are scored once that round is.  Returns the groups written. */
-static size_t
-sb_describe_rounds(s3a_uttdec_t *ud, const float *const *feat_dev, const int32_t *n_frames, int32_t n1, const int32_t *order, int32_t lead_g, int32_t R,
-                   std::vector<size_t> &rd_g, std::vector<int32_t> &rd_f)
-{
-    const size_t S_ = (size_t)ud->S.n_sen;
-    const int32_t DP = ud->S.D4 * 4;
-    size_t row = 0, g = 0;
-    long long max_g = 0;
-    for (int32_t k = 0; k < n1; k++) {
-        const int32_t u = order[k];
-        ud->sb_row0.h[u] = (long long)row;
-        row += (size_t)n_frames[u];
-        max_g = max(max_g, (long long)(n_frames[u] + UW_FB - 1) / UW_FB);
-    }
-    rd_g.assign(1, 0); rd_f.clear();
-    for (long long a = 0; a < max_g; ) {
-        const long long b = min(max_g, a + (a == 0 ? lead_g : R));
-        for (int32_t k = 0; k < n1; k++) {
-            const int32_t u = order[k];
-            const size_t r0 = (size_t)ud->sb_row0.h[u];
-            for (long long j = a; j < b && j * UW_FB < n_frames[u]; j++, g++) {
-                const int32_t j0 = (int32_t)j * UW_FB;
-                UwGroup &gr = ud->sb_gdesc.h[g];
-                gr.feat = feat_dev[u] + (size_t)j0 * DP;
-                gr.win = ud->sb_scores.d + (r0 + j0) * S_;
-                gr.winb = ud->sb_bests.d + (r0 + j0) * S_;
-                gr.nv = min(UW_FB, n_frames[u] - j0); gr.pad = 0;
-            }
-        }
-        rd_g.push_back(g); rd_f.push_back((int32_t)(b * UW_FB));
-        a = b;
-    }
-    return g;
+    for (size_t u = 0; u < n_utt; u++) ud->sb_row0.h[u] = (long long)P.row0[u];
+    HIPCHK(hipMemcpyAsync(ud->sb_gdesc.d, ud->sb_gdesc.h, P.groups.size() * sizeof(UwGroup), hipMemcpyHostToDevice, ud->stream));
+    HIPCHK(hipMemcpyAsync(ud->sb_row0.d, ud->sb_row0.h, n_utt * 8, hipMemcpyHostToDevice, ud->stream));
+    return S3A_OK;
 }
 
 /* score the groups [g0, g0 + n_g) of the uploaded table: launches of up to SB_PIECE groups */
@@ -4775,17 +4730,14 @@ kf_static_group(s3a_uttdec_t *ud, int32_t m, const long long *row0, size_t g0, s
 static int32_t
 kf_decode_static(s3a_uttdec_t *ud, int32_t n_utt, const int32_t *n_frames)
 {
-    size_t rows = 0, groups = 0;
+    const KfPlan P = kf_plan(n_utt, n_frames, KFP_ONE, 0, true, 0, 0, 0, false);
+    if (P.max_rows > sb_budget_rows(ud)) return S3A_EUNSUP;
     std::vector<const float *> fd((size_t)n_utt);
-    for (int32_t z = 0; z < n_utt; z++) { rows += (size_t)n_frames[z]; groups += (size_t)(n_frames[z] + UW_FB - 1) / UW_FB; fd[z] = ud->h_ctx_up[z].feat; }
-    if (rows > sb_budget_rows(ud)) return S3A_EUNSUP;
+    for (int32_t z = 0; z < n_utt; z++) fd[z] = ud->h_ctx_up[z].feat;
     int32_t rc;
-    if ((rc = sb_reserve(ud, rows, groups, (size_t)n_utt)) != S3A_OK) return rc;
-    const size_t ng = sb_describe(ud, fd.data(), n_frames, 0, n_utt, 0);
-    HIPCHK(hipMemcpyAsync(ud->sb_gdesc.d, ud->sb_gdesc.h, ng * sizeof(UwGroup), hipMemcpyHostToDevice, ud->stream));
-    HIPCHK(hipMemcpyAsync(ud->sb_row0.d, ud->sb_row0.h, (size_t)n_utt * 8, hipMemcpyHostToDevice, ud->stream));
+    if ((rc = sb_load(ud, P, fd.data())) != S3A_OK) return rc;
     ud->kf_n_score = ud->kf_n_frames = 0;
-    return kf_static_group(ud, n_utt, ud->sb_row0.d, 0, ng);
+    return kf_static_group(ud, n_utt, ud->sb_row0.d, 0, P.groups.size());
 }
 
 /* s3a_uttdec_decode_queue through ku_frames: the lanes take the utterances themselves.  The queue goes through in as many parts as
@@ -4795,106 +4747,73 @@ kf_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat_dev, c
                 int32_t *wcount)
 {
     const size_t budget = sb_budget_rows(ud);
-    /* the parts: consecutive utterances whose rows fit */
-    std::vector<int32_t> cut(1, 0);
-    size_t rows = 0, max_rows = 0, groups = 0;
-    for (int32_t u = 0; u < n_utt; u++) {
-        if (rows > 0 && rows + (size_t)n_frames[u] > budget) { cut.push_back(u); rows = 0; }
-        rows += (size_t)n_frames[u];
-        max_rows = max(max_rows, rows);
-        groups += (size_t)(n_frames[u] + UW_FB - 1) / UW_FB;
-    }
-    cut.push_back(n_utt);
-    if (max_rows > budget) { s3a_set_error("s3a_uttdec_decode_queue: an utterance's scores (%zu rows) do not fit the device", max_rows); return S3A_ENOMEM; }
-    int32_t rc;
-    if ((rc = sb_reserve(ud, max_rows, groups, (size_t)n_utt)) != S3A_OK) return rc;
-    /* the order of the takes: within a part the longest utterance first (stable: equal lengths in queue order) -- the launch ends with its
-     * slowest lane, and an utterance taken when the counter is nearly through should be a short one */
-    if ((rc = q_reserve(ud, ud->kf_order, S3A_GROW_DEV | S3A_GROW_PIN, (size_t)n_utt, "queue order")) != S3A_OK) return rc;
-    for (size_t k = 0; k + 1 < cut.size(); k++) {
-        for (int32_t u = cut[k]; u < cut[k + 1]; u++) ud->kf_order.h[u] = u;
-        if (!s3a_variants()->kf_queue_in_order)
-            std::stable_sort(ud->kf_order.h + cut[k], ud->kf_order.h + cut[k + 1], [&](int32_t a, int32_t b) { return n_frames[a] > n_frames[b]; });
-    }
     /* SCORING BESIDE THE SEARCH (kf_launch_overlapped): only a LEAD of the first n1 takes' utterances -- their first kf_overlap_lead frames --
      * is scored up front; the rest is scored by the companion shape in the halves of the CUs that n1 lanes leave free: first those utterances'
      * later frames in rounds of R groups each, with *f_ready saying how far all of them are scored, then the other utterances; the other lanes
      * start when it is through.  (kf_overlap_whole: the first n1 utterances WHOLE up front, as before the rounds.)  Only where the plan's
      * premise holds -- an engine that sizes its launches for the whole device (as the relay), two lanes per CU, more utterances than lanes --
-     * and only for the plain call: one part, no second pass, no look-ahead heuristic, no kept lattices.  s3a_variants_t: kf_overlap = 1
-     * asks for it (KF_OVERLAP_DEFAULT: without being asked), kf_overlap_n1 > 0 forces it with that many first lanes (the tests' small
-     * engines; the caller answers for co-residency), kf_no_overlap: never. */
+     * and only for the plain call: one part (the plan drops n1 otherwise), no second pass, no look-ahead heuristic, no kept lattices.
+     * s3a_variants_t: kf_overlap = 1 asks for it (KF_OVERLAP_DEFAULT: without being asked), kf_overlap_n1 > 0 forces it with that many first
+     * lanes (the tests' small engines; the caller answers for co-residency), kf_no_overlap: never. */
     const s3a_variants_t *va = s3a_variants();
     int32_t n1 = 0;
-    if (!va->kf_no_overlap && cut.size() == 2 && !ud->dag && ud->S.pheurtype == 0 && !ud->q_keep_lat && n_utt > ud->n_lanes && ud->kf_cluster_opt == 0
-        && ud->d_kfleft) {
+    if (!va->kf_no_overlap && !ud->dag && ud->S.pheurtype == 0 && !ud->q_keep_lat && n_utt > ud->n_lanes && ud->kf_cluster_opt == 0 && ud->d_kfleft) {
         const int32_t n_cu = max(1, ud->g->dev->n_cu);
         if (va->kf_overlap_n1 > 0) { if (va->kf_overlap_n1 < ud->n_lanes) n1 = va->kf_overlap_n1; }
         else if ((KF_OVERLAP_DEFAULT || va->kf_overlap) && kf_alone(ud) && ud->n_lanes > n_cu && ud->n_lanes / 2 <= n_cu && kf_choose_c(ud, ud->n_lanes) == 1)
             n1 = ud->n_lanes / 2;
     }
-    if (n1 > 0) {
-        if (!ud->kf_stream2 && hipStreamCreateWithFlags(&ud->kf_stream2, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ud->kf_stream2 = NULL; n1 = 0; }
+    const int32_t lead_g = (max(0, va->kf_overlap_lead) + UW_FB - 1) / UW_FB;
+    const auto plan = [&](int32_t first) {
+        return kf_plan(n_utt, n_frames, KFP_BUDGET, budget, va->kf_queue_in_order != 0, first, lead_g > 0 ? lead_g : KF_OVERLAP_LEAD / UW_FB,
+                       va->kf_overlap_round > 0 ? va->kf_overlap_round : max(1, SB_PIECE / max(1, first)), va->kf_overlap_whole != 0);
+    };
+    KfPlan K = plan(n1);
+    if (K.max_rows > budget) { s3a_set_error("s3a_uttdec_decode_queue: an utterance's scores (%zu rows) do not fit the device", K.max_rows); return S3A_ENOMEM; }
+    if (K.n1 > 0) {                 /* (the second stream and the events that order the two: without them, the plan without first lanes) */
+        bool have = ud->kf_stream2 || hipStreamCreateWithFlags(&ud->kf_stream2, hipStreamNonBlocking) == hipSuccess;
+        if (!have) { (void)hipGetLastError(); ud->kf_stream2 = NULL; }
         for (auto &e : ud->kf_ov_ev)
-            if (n1 > 0 && !e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); e = NULL; n1 = 0; }
+            if (have && !e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); e = NULL; have = false; }
+        if (!have) K = plan(0);
     }
+    n1 = K.n1;
+    int32_t rc;
+    if ((rc = q_reserve(ud, ud->kf_order, S3A_GROW_DEV | S3A_GROW_PIN, (size_t)n_utt, "queue order")) != S3A_OK) return rc;
     ud->kf_overlapped = n1 > 0 ? 1 : 0;
-    ud->kf_lead = 0;
-    std::vector<size_t> g_at(cut.size(), 0), g_end, rd_g;
-    std::vector<int32_t> rd_f;
-    size_t g_first = 0;             /* (the plan: the groups of the first n1 takes' utterances) */
-    if (n1 > 0) {
-        if (va->kf_overlap_whole) g_first = sb_describe(ud, feat_dev, n_frames, 0, n1, 0, ud->kf_order.h);
-        else {
-            const int32_t lead_g = (max(0, va->kf_overlap_lead) + UW_FB - 1) / UW_FB;
-            g_first = sb_describe_rounds(ud, feat_dev, n_frames, n1, ud->kf_order.h, lead_g > 0 ? lead_g : KF_OVERLAP_LEAD / UW_FB,
-                                         va->kf_overlap_round > 0 ? va->kf_overlap_round : max(1, SB_PIECE / n1), rd_g, rd_f);
-            if (!rd_f.empty()) ud->kf_lead = rd_f[0];
-        }
-        /* (one run of rows over both pieces: the second piece's rows go on where the first one's end) */
-        const size_t rows1 = (size_t)ud->sb_row0.h[ud->kf_order.h[n1 - 1]] + (size_t)n_frames[ud->kf_order.h[n1 - 1]];
-        g_at[1] = g_first + sb_describe(ud, feat_dev, n_frames, n1, n_utt, g_first, ud->kf_order.h);
-        for (int32_t k = n1; k < n_utt; k++) ud->sb_row0.h[ud->kf_order.h[k]] += (long long)rows1;
-        for (size_t g = g_first; g < g_at[1]; g++) { ud->sb_gdesc.h[g].win += rows1 * (size_t)ud->S.n_sen; ud->sb_gdesc.h[g].winb += rows1 * (size_t)ud->S.n_sen; }
-        g_end.resize((size_t)n_utt);
-        size_t gq = 0;
-        for (int32_t k = 0; k < n_utt; k++) { gq += (size_t)(n_frames[ud->kf_order.h[k]] + UW_FB - 1) / UW_FB; g_end[k] = gq; }
-        /* (the launches' argument slots: none of this call's launches may have to wait for a slot -- the host would wait for ku_frames #1 with
-         * the companion's launches still in its hands) */
-        if (ud->kf_arg_at % KF_ARG_SLOTS + 2 + KF_STAGES > KF_ARG_SLOTS) {
-            HIPCHK(hipStreamSynchronize(ud->stream));
-            HIPCHK(hipStreamSynchronize(ud->kf_stream2));
-            ud->kf_arg_at = 0;
-        }
+    ud->kf_lead = K.lead;
+    /* (the launches' argument slots: none of this call's launches may have to wait for a slot -- the host would wait for ku_frames #1 with
+     * the companion's launches still in its hands) */
+    if (n1 > 0 && ud->kf_arg_at % KF_ARG_SLOTS + 2 + KF_STAGES > KF_ARG_SLOTS) {
+        HIPCHK(hipStreamSynchronize(ud->stream));
+        HIPCHK(hipStreamSynchronize(ud->kf_stream2));
+        ud->kf_arg_at = 0;
     }
-    else
-        for (size_t k = 0; k + 1 < cut.size(); k++) g_at[k + 1] = g_at[k] + sb_describe(ud, feat_dev, n_frames, cut[k], cut[k + 1], g_at[k]);
-    HIPCHK(hipMemcpyAsync(ud->sb_gdesc.d, ud->sb_gdesc.h, g_at.back() * sizeof(UwGroup), hipMemcpyHostToDevice, ud->stream));
-    HIPCHK(hipMemcpyAsync(ud->sb_row0.d, ud->sb_row0.h, (size_t)n_utt * 8, hipMemcpyHostToDevice, ud->stream));
+    if ((rc = sb_load(ud, K, feat_dev)) != S3A_OK) return rc;
+    memcpy(ud->kf_order.h, K.order.data(), (size_t)n_utt * 4);
     HIPCHK(hipMemcpyAsync(ud->kf_order.d, ud->kf_order.h, (size_t)n_utt * 4, hipMemcpyHostToDevice, ud->stream));
     ud->kf_n_score = ud->kf_n_frames = 0;
-    for (size_t k = 0; k + 1 < cut.size(); k++) {
-        const int32_t u0 = cut[k], nu = cut[k + 1] - cut[k];
+    for (size_t k = 0; k + 1 < K.cut.size(); k++) {
+        const int32_t u0 = K.cut[k], nu = K.cut[k + 1] - K.cut[k];
         kf_mark(ud);
         /* (the lead through the companion shape: alone it is the faster of the two, profiles/r7_overlap_experiments.txt 0) */
-        if (n1 > 0 && !rd_f.empty()) rc = sb_score(ud, 0, rd_g[1], true);
-        else rc = sb_score(ud, g_at[k], n1 > 0 ? g_first : g_at[k + 1] - g_at[k]);
+        if (n1 > 0) rc = sb_score(ud, 0, K.g_lead, K.lead > 0);
+        else rc = sb_score(ud, K.g_at[k], K.g_at[k + 1] - K.g_at[k]);
         if (rc != S3A_OK) return rc;
         kf_mark(ud);
-        if (n1 > 0) {               /* (the counter, *q_ready = n1, the resumed lanes' counts, *f_ready = the lead; no lane has left) */
-            HIPCHK(hipMemsetAsync(ud->d_kfnext, 0, 16 * 4, ud->stream));
-            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(ud->d_kfnext + 1), n1, 1, ud->stream));
-            if (!rd_f.empty()) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(ud->d_kfnext + 3), rd_f.size() > 1 ? rd_f[0] : INT32_MAX, 1, ud->stream));
+        if (n1 > 0) {               /* (the counter, *q_ready = n1, the resumed lanes' counts, *f_ready; no lane has left) */
+            HIPCHK(hipMemsetAsync(ud->d_kfnext, 0, KFN_LANE * 4, ud->stream));
+            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(ud->d_kfnext + KFN_Q_READY), n1, 1, ud->stream));
+            if (K.lead > 0) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(ud->d_kfnext + KFN_F_READY), K.f_ready0, 1, ud->stream));
             HIPCHK(hipMemsetAsync(ud->d_kfleft, 0, (size_t)ud->n_lanes * 4, ud->stream));
         }
-        else HIPCHK(hipMemsetAsync(ud->d_kfnext, 0, 4, ud->stream));
+        else HIPCHK(hipMemsetAsync(ud->d_kfnext + KFN_COUNTER, 0, 4, ud->stream));
         KfJob J;
         memset(&J, 0, sizeof J);
-        J.mode = KF_QUEUE; J.n_utt = nu; J.u0 = u0; J.order = ud->kf_order.d; J.next = ud->d_kfnext; J.lane_u = ud->d_kfnext + 16; J.stage = ud->q_ctx.d;
+        J.mode = KF_QUEUE; J.n_utt = nu; J.u0 = u0; J.order = ud->kf_order.d; J.next = ud->d_kfnext + KFN_COUNTER; J.lane_u = ud->d_kfnext + KFN_LANE; J.stage = ud->q_ctx.d;
         J.row0 = ud->sb_row0.d; J.scores = ud->sb_scores.d; J.bests = ud->sb_bests.d;
         J.hdr = ud->q_hdr.d; J.words = ud->q_words.d; J.wcount = wcount; J.P = P; J.B = B; J.n_word = ud->cfg.n_word;
-        const KfOverlap ov = { n1, g_first, g_at[1] - g_first, g_end.data(), (int32_t)rd_f.size(), 1, va->kf_overlap_hold != 0, rd_g.data(), rd_f.data() };
-        if ((rc = kf_launch_chain(ud, min(ud->n_lanes, nu), J, n1 > 0 ? &ov : NULL)) != S3A_OK) return rc;
+        if ((rc = kf_launch_chain(ud, min(ud->n_lanes, nu), J, n1 > 0 ? &K : NULL)) != S3A_OK) return rc;
         ud->kf_n_frames++;
         kf_mark(ud);
     }
@@ -5208,6 +5127,27 @@ s3a_queue_schedule(int32_t n_lanes, int32_t boundary, int32_t n_utt, const int32
     }
 }
 
+/* the plan of a ku_frames call (s3a_kfplan.h) as flat arrays: host arithmetic, no device */
+extern "C" int32_t
+s3a_kf_queue_plan(int32_t n_utt, const int32_t *n_frames, int32_t rule, int64_t budget, int32_t in_order, int32_t n1, int32_t lead_groups,
+                  int32_t round_groups, int32_t whole, int64_t *sizes, int32_t *order, int32_t *cut, int64_t *row0, int64_t *g_at,
+                  int64_t *groups, int64_t *steps)
+{
+    if (n_utt <= 0 || !n_frames || !sizes || rule < KFP_BUDGET || rule > KFP_ONE || budget < 0 || n1 < 0) return S3A_EINVAL;
+    for (int32_t u = 0; u < n_utt; u++) if (n_frames[u] <= 0) return S3A_EINVAL;
+    const KfPlan P = kf_plan(n_utt, n_frames, rule, (size_t)budget, in_order != 0, n1, lead_groups, round_groups, whole != 0);
+    const int64_t sz[9] = { (int64_t)P.cut.size() - 1, (int64_t)P.groups.size(), (int64_t)P.script.size(), (int64_t)P.max_rows, P.n1,
+                            (int64_t)P.g_first, (int64_t)P.g_lead, P.lead, P.f_ready0 };
+    std::copy(sz, sz + 9, sizes);
+    if (!order) return S3A_OK;
+    if (!cut || !row0 || !g_at || !groups || !steps) return S3A_EINVAL;
+    std::copy(P.order.begin(), P.order.end(), order); std::copy(P.cut.begin(), P.cut.end(), cut);
+    std::copy(P.row0.begin(), P.row0.end(), row0); std::copy(P.g_at.begin(), P.g_at.end(), g_at);
+    for (const KfGroup &g : P.groups) { *groups++ = g.utt; *groups++ = g.first; *groups++ = g.frames; *groups++ = g.row; }
+    for (const KfStep &s : P.script) { *steps++ = s.op; *steps++ = s.a; *steps++ = s.b; }
+    return S3A_OK;
+}
+
 /* s3a_uttdec_queue_keep_lattices: the lanes `lanes[0 .. n)` have just gone through the second pass for the utterances utts[]: wait for the
  * stream and read their lattices back, before the lanes' tables are reused (the price of lattices out of a queue: the host waits once per
  * group / refill event) */
@@ -5266,19 +5206,6 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
      * with refill events, or -- asked for -- window blocks, the regime that lost to the launches. */
     /* (-pheurtype goes the same way: the look-ahead's tables are a LANE's -- made when the lane begins its utterance, ku_ci_ahead / ku_phn_heur) */
     bool kfd = !graph_mode && kf_served(ud, min(ud->n_lanes, n_utt)) && (ud->dag != NULL || S.pheurtype > 0);
-    std::vector<int32_t> kfd_order;
-    if (kfd) {
-        kfd_order.resize((size_t)n_utt);
-        for (int32_t u = 0; u < n_utt; u++) kfd_order[u] = u;
-        std::stable_sort(kfd_order.begin(), kfd_order.end(), [&](int32_t a, int32_t b) { return n_frames[a] > n_frames[b]; });
-        size_t rows = 0, worst = 0;
-        for (int32_t k = 0; k < n_utt; k++) {
-            if (k % ud->n_lanes == 0) rows = 0;
-            rows += (size_t)max(n_frames[kfd_order[k]], 0);
-            worst = max(worst, rows);
-        }
-        if (worst > sb_budget_rows(ud)) kfd = false;            /* (a group's scores do not fit: the launches) */
-    }
     /* utterances begin at window boundaries (the look-ahead pass scores K frames of all lanes); in graph mode at the blocks' */
     const int32_t n = min(ud->n_lanes, n_utt), E = graph_mode ? graph_block_frames(ud) : (S.win_K > 0 ? S.win_K : 1), D4x4 = S.D4 * 4, T = S.T;
     int32_t rc;
@@ -5290,6 +5217,11 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
         if (n_frames[u] <= 0 || n_frames[u] > ud->max_frames) { s3a_set_error("s3a_uttdec_decode_queue: utterance %d has %d frames (1..%d)", u, n_frames[u], ud->max_frames); return S3A_EINVAL; }
         if (!feat[u]) { s3a_set_error("s3a_uttdec_decode_queue: utterance %d has no features", u); return S3A_EINVAL; }
         row0[u + 1] = row0[u] + (size_t)n_frames[u];
+    }
+    KfPlan K;                       /* (kfd: the groups are the plan's parts) */
+    if (kfd) {
+        K = kf_plan(n_utt, n_frames, KFP_LANES, (size_t)ud->n_lanes, false, 0, 0, 0, false);
+        if (K.max_rows > sb_budget_rows(ud)) kfd = false;           /* (a group's scores do not fit: the launches) */
     }
     /* features: one buffer, rows padded to the scorer's float4 stride, one copy */
     std::vector<const float *> fd((size_t)n_utt);
@@ -5327,10 +5259,10 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
             if ((rc = utt_context(ud, ud->q_ctx.h[u], fd[u], n_frames[u], 1, 0, u)) != S3A_OK) return rc;
         for (int32_t z = 0; z < n; z++) ud->lane[z].nfr = 0;
         if (kfd) {              /* the groups' lane / utterance lists: [lanes 0 .. m - 1][their utterances] per group */
-            for (int32_t k0 = 0; k0 < n_utt; k0 += ud->n_lanes) {
-                const int32_t m = min(ud->n_lanes, n_utt - k0);
+            for (size_t p = 0; p + 1 < K.cut.size(); p++) {
+                const int32_t k0 = K.cut[p], m = K.cut[p + 1] - k0;
                 for (int32_t z = 0; z < m; z++) sched.push_back(z);
-                for (int32_t z = 0; z < m; z++) { sched.push_back(kfd_order[k0 + z]); last_utt[z] = kfd_order[k0 + z]; }
+                for (int32_t z = 0; z < m; z++) { sched.push_back(K.order[k0 + z]); last_utt[z] = K.order[k0 + z]; }
             }
         }
     }
@@ -5410,30 +5342,15 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
         if (rc == S3A_OK) rc = kf_decode_queue(ud, n_utt, fd.data(), n_frames, B, P, wcount);
     }
     else if (kfd) {
-        /* every group's scoring groups and rows described up front (the pinned tables must not change under the copies in flight) */
-        size_t groups = 0, max_rows = 0;
-        std::vector<size_t> g_at(1, 0);
-        std::vector<const float *> gf((size_t)n_utt);
-        std::vector<int32_t> gn((size_t)n_utt);
-        for (int32_t k = 0; k < n_utt; k++) { gf[k] = fd[kfd_order[k]]; gn[k] = n_frames[kfd_order[k]]; groups += (size_t)(gn[k] + UW_FB - 1) / UW_FB; }
-        for (int32_t k0 = 0; k0 < n_utt; k0 += ud->n_lanes) {
-            size_t rows = 0;
-            for (int32_t k = k0; k < min(n_utt, k0 + ud->n_lanes); k++) rows += (size_t)gn[k];
-            max_rows = max(max_rows, rows);
-        }
-        if (rc == S3A_OK) rc = sb_reserve(ud, max_rows, groups, (size_t)n_utt);
-        for (int32_t k0 = 0; k0 < n_utt && rc == S3A_OK; k0 += ud->n_lanes)         /* (rows restart per group: sb_describe; row0 by position in the order) */
-            g_at.push_back(g_at.back() + sb_describe(ud, gf.data(), gn.data(), k0, min(n_utt, k0 + ud->n_lanes), g_at.back()));
-        if (rc == S3A_OK && (hipMemcpyAsync(ud->sb_gdesc.d, ud->sb_gdesc.h, g_at.back() * sizeof(UwGroup), hipMemcpyHostToDevice, ud->stream) != hipSuccess
-                             || hipMemcpyAsync(ud->sb_row0.d, ud->sb_row0.h, (size_t)n_utt * 8, hipMemcpyHostToDevice, ud->stream) != hipSuccess)) rc = S3A_EHIP;
+        /* every group's scoring groups and rows loaded up front (the pinned tables must not change under the copies in flight) */
+        if (rc == S3A_OK) rc = sb_load(ud, K, fd.data());
         ud->kf_n_score = ud->kf_n_frames = 0;
-        size_t gi = 0;
-        for (int32_t k0 = 0; k0 < n_utt && rc == S3A_OK; k0 += ud->n_lanes, gi++) {
-            const int32_t m = min(ud->n_lanes, n_utt - k0);
+        for (size_t p = 0; p + 1 < K.cut.size() && rc == S3A_OK; p++) {
+            const int32_t k0 = K.cut[p], m = K.cut[p + 1] - k0;
             const int32_t *bl = ud->q_sched.d + (size_t)2 * k0, *bu = bl + m;
             hipLaunchKernelGGL(ku_lanes_begin, dim3(32, 1, m), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, B, bl, bu, (const UCtx *)ud->q_ctx.d);
-            if ((rc = enqueue_pheur_tables(ud, gn[k0], m, bl)) != S3A_OK) break;       /* (the group's longest utterance is its first) */
-            if ((rc = kf_static_group(ud, m, ud->sb_row0.d + k0, g_at[gi], g_at[gi + 1] - g_at[gi])) != S3A_OK) break;
+            if ((rc = enqueue_pheur_tables(ud, n_frames[K.order[k0]], m, bl)) != S3A_OK) break;       /* (the group's longest utterance is its first) */
+            if ((rc = kf_static_group(ud, m, ud->sb_row0.d + k0, K.g_at[p], K.g_at[p + 1] - K.g_at[p])) != S3A_OK) break;
             rc = enqueue_utts_end(ud, m, bl, bu, sched.data() + (size_t)2 * k0, sched.data() + (size_t)2 * k0 + m, P, n_utt, wcount);
         }
     }
@@ -5583,7 +5500,7 @@ s3a_uttdec_last_overlap(s3a_uttdec_t *ud, int32_t *overlapped, int32_t *resumed)
         *resumed = 0;
         if (ud->kf_overlapped) {
             HIPCHK(hipSetDevice(ud->device));
-            HIPCHK(hipMemcpy(resumed, ud->d_kfnext + 2, 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(resumed, ud->d_kfnext + KFN_RESUMED, 4, hipMemcpyDeviceToHost));
         }
     }
     return S3A_OK;
@@ -5598,7 +5515,7 @@ s3a_uttdec_last_overlap2(s3a_uttdec_t *ud, int32_t *left_inside, int32_t *lead)
         *left_inside = 0;
         if (ud->kf_overlapped) {
             HIPCHK(hipSetDevice(ud->device));
-            HIPCHK(hipMemcpy(left_inside, ud->d_kfnext + 4, 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(left_inside, ud->d_kfnext + KFN_INSIDE, 4, hipMemcpyDeviceToHost));
         }
     }
     return S3A_OK;

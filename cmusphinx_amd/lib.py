@@ -210,6 +210,7 @@ _SIGS = {
     "s3a_uttdec_decode_queue": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     "s3a_uttdec_decode_queue_dev": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     "s3a_queue_schedule": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3a_kf_queue_plan": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 7),
     "s3a_uttdec_queue_status": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "s3a_uttdec_queue_hyp": (C.c_int32, [C.c_void_p, C.c_int32, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     "s3a_uttdec_result": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
@@ -346,6 +347,25 @@ def queue_schedule(n_lanes, boundary, n_frames):
     if total < 0:
         raise S3AError(f"s3a_queue_schedule: error {total}")
     return lane, f0, int(total)
+
+
+def kf_queue_plan(n_frames, rule, budget, in_order=False, n1=0, lead_groups=0, round_groups=0, whole=False):
+    """the plan of a ku_frames call (csrc/s3a_kfplan.h; host arithmetic) -> dict: order, cut, row0, g_at, groups [n, 4] (utterance, first
+    frame, frames, row), steps [n, 3] (op, a, b) and the plan's scalars"""
+    nf = np.ascontiguousarray(n_frames, np.int32)
+    sizes = np.zeros(9, np.int64)
+    args = (len(nf), _p(nf), int(rule), int(budget), int(in_order), int(n1), int(lead_groups), int(round_groups), int(whole), _p(sizes))
+    rc = load().s3a_kf_queue_plan(*args, *[None] * 6)
+    if rc != S3A_OK:
+        raise S3AError(f"s3a_kf_queue_plan: error {rc}")
+    parts, n_g, n_s = (int(x) for x in sizes[:3])
+    out = {"order": np.zeros(len(nf), np.int32), "cut": np.zeros(parts + 1, np.int32), "row0": np.zeros(len(nf), np.int64),
+           "g_at": np.zeros(parts + 1, np.int64), "groups": np.zeros((n_g, 4), np.int64), "steps": np.zeros((n_s, 3), np.int64)}
+    rc = load().s3a_kf_queue_plan(*args, *[_p(a) for a in out.values()])
+    if rc != S3A_OK:
+        raise S3AError(f"s3a_kf_queue_plan: error {rc}")
+    out.update(zip(("max_rows", "n1", "g_first", "g_lead", "lead", "f_ready0"), (int(x) for x in sizes[3:])))
+    return out
 
 
 def device_count() -> int:

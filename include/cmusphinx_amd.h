@@ -821,6 +821,16 @@ int32_t s3a_uttdec_queue_status(s3a_uttdec_t *ud, int32_t utt, int32_t *err, int
  * window, s3a_uttdec_window; 1 without look-ahead scoring).  Returns the engine frames the whole queue takes. */
 int32_t s3a_queue_schedule(int32_t n_lanes, int32_t boundary, int32_t n_utt, const int32_t *n_frames,
                            int32_t *lane, int32_t *f0);
+/* the plan of a call that goes through ku_frames (csrc/s3a_kfplan.h has the terms), host arithmetic on the lengths alone (no device):
+ * rule 0 = the plain queue (parts of `budget` rows), 1 = the second-pass queue (longest first, parts of `budget` lanes), 2 = one part,
+ * lane z = utterance z; n1 > 0: the first n1 takes scored beside the search, a lead of lead_groups groups up front, rounds of
+ * round_groups (`whole`: those utterances whole up front).  sizes[9] = parts, groups, steps, the largest part's rows, n1 as planned,
+ * the first takes' groups, those scored up front, the lead's frames, *f_ready at the start.  order = NULL: the sizes only; else all of
+ * order[n_utt], cut[parts + 1], row0[n_utt], g_at[parts + 1], groups[4 x groups] (utterance, first frame, frames, row) and
+ * steps[3 x steps] (0 = score the groups [a, b) | 1 = *f_ready = a | 2 = *q_ready = a; a; b), the caller's. */
+int32_t s3a_kf_queue_plan(int32_t n_utt, const int32_t *n_frames, int32_t rule, int64_t budget, int32_t in_order, int32_t n1,
+                          int32_t lead_groups, int32_t round_groups, int32_t whole, int64_t *sizes, int32_t *order, int32_t *cut,
+                          int64_t *row0, int64_t *g_at, int64_t *groups, int64_t *steps);
 /* diagnostics: time lane z's last utterance spent in each phase of the one-workgroup word level, in 100 MHz ticks
  * ([0] frame record + exits, [1] P1, [2] P2 trigram scores, [3] P3 hash insert, [4] P4 entry places, [5] P5 staging,
  * [6] pruning, [7] table + LM contexts, [8] word transitions) */
