@@ -28,6 +28,7 @@
 #include <string.h>
 #include <limits.h>
 #include <vector>
+#include <deque>
 #include <map>
 #include <atomic>
 #include <mutex>
@@ -46,6 +47,7 @@
 #include "s3a_dag.h"
 #include "s3a_hostmem.h"
 #include "s3a_kfplan.h"
+#include "s3a_uttgeom.h"
 
 /* A pointer that came out of a structure in memory is a GENERIC pointer to the compiler; what it makes of an access through one is
  * flat_load / flat_store -- counted by the LDS counter as well as the memory counter, so that every wait for an LDS read waits for
@@ -604,7 +606,7 @@ struct UwGroup {
 };
 
 /* (NT == 256: at most 256 VGPRs, a wave per SIMD beside the two of a ku_frames workgroup -- the COMPANION shape <.., true, 256>,
- * uw_geometry_companion; the 512-thread shapes have that budget by their size) */
+ * ug_companion, s3a_uttgeom.h; the 512-thread shapes have that budget by their size) */
 template <int CP, bool EXACT, bool TAB_LDS, int NT>
 __global__ void __launch_bounds__(NT, NT == 256 ? 2 : 1)
 ku_score_window(const ULane *__restrict__ lanes, UShared S, int32_t n_lanes, int32_t f0, int32_t K, int32_t fpc,
@@ -761,12 +763,6 @@ uw_one_gaussian(const UShared &S, int32_t g, const float *__restrict__ x)
  * USEL_G workgroups per lane; every one works out the CI maximum for itself (n_ci_sen loads from one row).
  */
 #define USEL_G 8
-#ifndef G_ENTER2_MANY
-#define G_ENTER2_MANY 12   /* ku_enter2's workgroups per lane from 64 lanes on (they take the calls in turn) */
-#endif
-#ifndef G_HIST_MANY
-#define G_HIST_MANY 9      /* ku_hist_count's workgroups per (tree, lane) with many lanes (5: 440.1, 7: 445.1, 8: 440.4, 9: 447.5 k frames/s) */
-#endif
 /* (NT threads; workgroup bx of G takes every G-th run of NT CD senones and leaves its maxima / counters in column bx of gpart[]) */
 template <bool EXACT, int NT>
 __device__ __forceinline__ void
@@ -1359,15 +1355,12 @@ ku_resolve(const ULane *__restrict__ lanes, UShared S, int32_t fg)
 #define UR_K 8
 /* ... and the not active ones from the frame's list of stamped parent sets instead of the sweep (GL one-wave workgroups per lane
  * behind the GA of the active HMMs) */
-#ifndef UR_GL
-#define UR_GL 192     /* one-wave workgroups per lane that walk the listed sets (one box: 128: 353.5 k, 256: 362.2 k, 512: 363.9 k frames/s; the sweep: 355.9 k) */
-#endif
 template <bool HEUR>
 __global__ void __launch_bounds__(RSBLOCK)
 ku_resolve_plist(const ULane *__restrict__ lanes, UShared S, int32_t fg)
 {
     LANE;
-    const int32_t GA = (int32_t)gridDim.x - UR_GL;
+    const int32_t GA = (int32_t)gridDim.x - UGT_UR_GL;
     if ((int32_t)blockIdx.x < GA) {
         d_dec_resolve_utt<UR_K, uint8_t, HEUR>(S.N, S.T, f, frame_beams(S, f), L.best, nact_cur, S.node_base, S.tree_of, S.prob,
                       S.par_off, S.par, L.pos, L.posf, L.sc, L.hist, L.outs, L.outh, L.bests, L.frame, L.turn, L.selfemit,
@@ -1378,7 +1371,7 @@ ku_resolve_plist(const ULane *__restrict__ lanes, UShared S, int32_t fg)
     d_dec_resolve_children<uint8_t, HEUR>(S.N, S.T, f, frame_beams(S, f), L.best, nact_cur, S.node_base, S.tree_of, S.prob,
                   S.par_off, S.par, L.pos, L.posf, L.sc, L.hist, L.outs, L.outh, L.bests, L.frame, L.turn, L.selfemit,
                   L.cnt, L.key, L.first, L.hbin, S.ps, L.pstamp8, S.rootnodes, S.n_rootnodes, L.propf, L.posout,
-                  L.plist, L.pcnt[f & 1], S.psmem_off, S.psmem, (int32_t)blockIdx.x - GA, UR_GL, UHX);
+                  L.plist, L.pcnt[f & 1], S.psmem_off, S.psmem, (int32_t)blockIdx.x - GA, UGT_UR_GL, UHX);
 }
 
 template <bool HEUR, int URK = UR_K>
@@ -1625,13 +1618,9 @@ ku_hyp(const ULane *__restrict__ lanes, WLm lm, WDict dict, UHypPar P, int32_t *
 static_assert(KF_NT == 512, "ku_frames: the word level's workgroup is the frame's workgroup");
 enum { KF_WINDOW, KF_STATIC, KF_QUEUE };
 #define KF_ST_WORDS 8
-#ifndef KF_OVERLAP_DEFAULT
-#define KF_OVERLAP_DEFAULT 1    /* scoring beside the search without being asked (kf_decode_queue; profiles/r7_overlap_experiments.txt) */
-#endif
-#ifndef KF_OVERLAP_LEAD
-#define KF_OVERLAP_LEAD 128     /* ... frames of each of the first utterances scored before the search begins (a multiple of 8; measured: at 64 no lane of the
+#define KF_OVERLAP_LEAD 128     /* frames of each of the first utterances scored before the search begins when a queue is scored beside it (kf_decode_queue;
+                                 * profiles/r7_overlap_experiments.txt; a multiple of 8; measured: at 64 no lane of the
                                  * bench's 256 first ones asks for an unscored frame, at 32 most do -- one step of margin, profiles/r8_rows_ahead_experiments.txt 2) */
-#endif
 #define KF_STAGES 2             /* launches a call's relay may have behind its first */
 
 union KfPool {                  /* phases that never overlap share this LDS */
@@ -3476,8 +3465,16 @@ struct s3a_uttdec_s {
     std::vector<int32_t> h_lcmap;
     int device;                 /* the device the engine lives on: made current at every entry point (HIP's current
                                  * device is per host thread, and engines are driven from several) */
-    int32_t many;               /* from this many lanes on: the grids / kernels for many lanes per launch (S3A_UTT_MANY; tests) */
-    int32_t g_eval, eval_block, g_ent, g_mark, g_res, scan_nc, scan_gc, hist_possible, weak_possible;
+    /* the launch geometry (s3a_uttgeom.h): what its rules read, kept current (gp_n: the lanes' scorers; pheurtype: s3a_uttdec_enable_pheur;
+     * kf_slots, kf_lds: asked once, of the ku_frames instantiation that is launched -- kf_query) | fixed at init | a frame's launches and
+     * the window's scoring pass per lanes of a call, made when a call first has that many (frame_geom; nothing they read changes after
+     * init) | what the call in progress adds (call_facts) */
+    UgShape shape;
+    UgEngine geom;
+    struct FrameGeom { int32_t n, hist_sort_launch; UgFrame fr; UgScore win; };
+    std::deque<FrameGeom> frame_geoms;
+    UgCall call;
+    const void *kf_asked;       /* the ku_frames instantiation shape.kf_slots and shape.kf_lds were asked of (NULL: none yet) */
     hipStream_t stream;
     int32_t n_utt;              /* lanes in use by the last decode */
     double last_decode_ms;
@@ -3486,13 +3483,9 @@ struct s3a_uttdec_s {
     std::vector<ProfEv> prof_ev;
     double prof_us[24];
     int64_t prof_n[24];
-    int32_t big_wl;             /* the word level's candidate phases as their own launches (wide beams) */
     hipEvent_t ev0, ev1;        /* around the frames of a decode (last_decode_ms) */
-    int32_t urk;                /* S3A_UTT_URK: nodes per thread of the resolve sweep (experiments) */
-    int32_t no_multi, gy;       /* tuning switches, read ONCE at init (S3A_UTT_NO_MULTI, S3A_UTT_GY; tests) */
     int32_t *d_dbg;             /* S3A_UTT_FRAMECHECK: [n_lanes][16] first broken invariant per lane */
     int32_t times;              /* S3A_UTT_TIMES: print the host-side phases of every decode call to stderr */
-    int32_t win_fpc;            /* S3A_UTT_WIN_FPC: slots per chunk of the look-ahead scoring (0: the cost model's) */
     UCtx *h_ctx_dn;             /* pinned [n_lanes]: the lanes' contexts after a decode (HostLane.h_ctx points into it) */
     int32_t *d_hyp_hdr, *h_hyp_hdr;     /* [n_lanes][UH_N]: ku_hyp's header per lane (device / pinned) */
     int32_t *d_hyp_words, *h_hyp_words; /* [n_lanes][hyp_wcap][6]: its words */
@@ -3503,8 +3496,6 @@ struct s3a_uttdec_s {
     int32_t keep_tables;        /* 0: with the second pass enabled the history tables stay on the device */
     int32_t tables_fetched, fstat_fetched;
     /* graph mode (s3a_uttdec_opts_t.graph): a block of frames captured once per lane count, replayed block after block */
-    int32_t use_graph;
-    int32_t scan_small_from;    /* lanes per launch from which ku_scan runs with 256-thread workgroups */
     int32_t *d_fgbase;
     struct FrameGraph { int32_t n, frames; hipGraphExec_t exec; UShared S; };
     std::vector<FrameGraph> graphs;
@@ -3523,9 +3514,6 @@ struct s3a_uttdec_s {
     struct QLat { s3a_lat_info_t info; std::vector<s3a_lat_node_t> nodes; std::vector<s3a_lat_link_t> links; int32_t have; };
     std::vector<QLat> q_lat;    /* [queue] ... and kept per utterance until the next decode */
     /* ku_frames: the frames of a window as one launch */
-    int32_t persist;            /* the engine's configuration is served and the option allows it */
-    int32_t kf_cluster_opt;     /* s3a_uttdec_opts_t.cluster */
-    int32_t kf_slots;           /* workgroups of ku_frames the device holds at once */
     int32_t *d_kfbar;           /* [n_lanes][2] the clusters' barrier counters, the XCDs their workgroups run on (a bit each) */
     int32_t kf_last_c;          /* workgroups per lane of the last launch (diagnostics) */
     int32_t kf_counted;         /* this engine is counted in g_kf_live */
@@ -3551,7 +3539,6 @@ struct s3a_uttdec_s {
     int32_t *d_kfleft;          /* [3 n_lanes] a lane left for want of scores | the frame | the utterance it left in, for a call without the relay's arrays */
     int32_t kf_overlapped;      /* the last call ran that plan */
     int32_t kf_lead;            /* ... frames of every first utterance scored before the search began (0: all) */
-    int32_t kf_comp_lds;        /* dynamic LDS a companion scoring workgroup may take beside one ku_frames workgroup (0: not asked yet) */
 };
 
 /* the words of s3a_uttdec_s.d_kfnext (KF_QUEUE): the takes' counter; with scoring beside the search the takes scored (*q_ready), the lanes
@@ -3676,10 +3663,8 @@ s3a_uttdec_opts_from_env(s3a_uttdec_opts_t *o)
     s3a_uttdec_opts_default(o);
     auto num = [](const char *name, int32_t dflt) { const char *v = getenv(name); return v ? (int32_t)atoi(v) : dflt; };
     o->many = num("S3A_UTT_MANY", 0); o->big_wl = num("S3A_UTT_BIGWL", -1); o->window = num("S3A_UTT_WIN", -1);
-    o->window_fpc = num("S3A_UTT_WIN_FPC", 0); o->g_eval = num("S3A_UTT_GEVAL", 0); o->g_res = num("S3A_UTT_GRES", 0);
-    o->scan_g = num("S3A_UTT_SCAN_G", 0); o->gy = num("S3A_UTT_GY", 0); o->sweep_k = num("S3A_UTT_URK", 0);
-    o->no_multi = getenv("S3A_UTT_NO_MULTI") != NULL; o->framecheck = getenv("S3A_UTT_FRAMECHECK") != NULL;
-    o->times = num("S3A_UTT_TIMES", 0); o->graph = num("S3A_UTT_GRAPH", 0); o->window_max = num("S3A_UTT_WIN_MAX", 0); o->scan_small_from = num("S3A_UTT_SCAN_SMALL", 0);
+    o->framecheck = getenv("S3A_UTT_FRAMECHECK") != NULL;
+    o->times = num("S3A_UTT_TIMES", 0); o->graph = num("S3A_UTT_GRAPH", 0); o->scan_small_from = num("S3A_UTT_SCAN_SMALL", 0);
     o->persist = num("S3A_UTT_PERSIST", 0); o->cluster = num("S3A_UTT_CLUSTER", 0); o->score_rows_max = num("S3A_UTT_SCORE_ROWS", 0);
 }
 
@@ -3793,49 +3778,21 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
     S.bm.hmmbeam = cfg->hmmbeam; S.bm.pbeam = cfg->pbeam; S.bm.wbeam = cfg->wbeam; S.bm.phone_uses_wbeam = 0;
     S.bm.maxhmmpf = cfg->maxhmmpf;
 
-    /* launch geometry: fixed grids, the kernels loop over the list lengths they find in memory */
-    ud->eval_block = (cfg->maxhmmpf >= EVBLOCK_LONG_LIST && maxn >= EVBLOCK_LONG_LIST) ? 256 : 64;
-    ud->no_multi = O.no_multi != 0;
+    /* launch geometry (s3a_uttgeom.h): fixed grids, the kernels loop over the list lengths they find in memory */
+    {
+        UgShape &s = ud->shape;
+        memset(&s, 0, sizeof s);
+        s.N = proto->N; s.T = T; s.maxn = maxn; s.ent_cap = proto->ent_cap; s.n_pset = proto->n_pset; s.n_emit = proto->n_emit; s.nodepk = S.nodepk != NULL;
+        s.n_sen = n_sen; s.n_ci_sen = n_ci_sen; s.n_cs = cs->n_comstate; s.CP = d->CP; s.D4 = d->D4; s.Gpad = d->Gpad; s.tab_size = (int32_t)d->tab_size;
+        s.max_cd = max_cd; s.tab16 = d->tab16 != NULL;          /* (gp_n: with the first lane's scorer, below) */
+        s.maxhmmpf = cfg->maxhmmpf; s.hmmbeam = cfg->hmmbeam; s.pbeam = cfg->pbeam; s.ptranskip = cfg->ptranskip;
+        s.n_cu = d->n_cu; s.n_lanes = n_lanes; s.exact = ud->exact;
+        s.many = O.many; s.big_wl = O.big_wl; s.window = O.window; s.scan_small_from = O.scan_small_from; s.persist = O.persist; s.cluster = O.cluster;
+        s.graph = O.graph; s.framecheck = O.framecheck;
+        ud->geom = ug_engine(s);
+    }
     if (O.framecheck && (!ud->mem.dev(ud->d_dbg, (size_t)n_lanes * 64) || hipMemset(ud->d_dbg, 0, (size_t)n_lanes * 64) != hipSuccess)) ud->d_dbg = NULL;
-    ud->gy = O.gy;
-    ud->many = O.many > 0 ? O.many : 32;
-    /* fixed grids, sized for the usual frame: a workgroup loops when a list is longer (virtual workgroups); with many
-     * lanes the idle workgroups of a generous grid cost more than the loop */
-    /* (many lanes: NOT a multiple of 16 -- measured with four 128-lane engines: 32 / 48 / 64 / 96 workgroups per (tree, lane) 406 /
-     * 424 / 411 / 409 k frames/s, 24 ... 72 otherwise 428 ... 438 k, odd counts best: consecutive (tree, lane) groups then start on
-     * rotating XCDs instead of piling every group's first, always busy, workgroup onto the same one) */
-#ifndef G_EVAL_MANY
-#define G_EVAL_MANY 57
-#endif
-    ud->g_eval = max(1, min((maxn + ud->eval_block - 1) / ud->eval_block, n_lanes >= ud->many ? G_EVAL_MANY : 2048 / max(1, min(n_lanes, 8))));
-    if (O.g_eval > 0) ud->g_eval = O.g_eval;
-#ifndef G_RES_MANY
-#define G_RES_MANY 49         /* (128: 401 k, 96: 403 k, 64: 405 k / 408.5 k, 48: 411 k, 32: 410 k frames/s; + UR_GL an odd total) */
-#endif
-    ud->g_res = max(1, min((proto->N + RSBLOCK - 1) / RSBLOCK, n_lanes >= ud->many ? G_RES_MANY : 1024));
-    if (O.g_res > 0) ud->g_res = O.g_res;
-    ud->urk = O.sweep_k > 0 ? O.sweep_k : UR_K;
-#ifndef G_ENT
-#define G_ENT 256
-#endif
-    ud->g_ent = max(1, min((proto->ent_cap + 255) / 256, G_ENT));
-    ud->g_mark = max(1, min((proto->ent_cap + M3BLOCK - 1) / M3BLOCK + ((maxn + M3BLOCK - 1) / M3BLOCK) * T, 1024));
-#ifndef G_MARK_MANY
-#define G_MARK_MANY 128
-#endif
-    if (n_lanes >= ud->many) ud->g_mark = min(ud->g_mark, G_MARK_MANY);     /* (many lanes: 1024 workgroups per lane were 131 k per launch, most of them idle: 50 -> 30 us per 128-lane launch, 331 -> 349 k frames/s) */
-    ud->scan_nc = (cfg->maxhmmpf >= SCAN_LONG_LIST && maxn >= SCAN_LONG_LIST) ? (maxn + SCAN_THREADS - 1) / SCAN_THREADS : 1;
-    ud->scan_gc = O.scan_g;
-    /* lextree_hmm_histbin can only fire when more than 1.5 x maxhmmpf HMMs can be active at all */
-    ud->hist_possible = (long long)proto->N > (long long)cfg->maxhmmpf + (cfg->maxhmmpf >> 1);
-    ud->weak_possible = cfg->ptranskip != 0 || cfg->pbeam < cfg->hmmbeam;
-    /* wide beams (thousands of word exits, 10^5..10^6 (exit, predecessor) candidates per frame): the word level's
-     * candidate phases run chip-wide as their own launches; opts->big_wl = 0 / 1 overrides */
-    ud->big_wl = O.big_wl >= 0 ? (O.big_wl != 0) : (cfg->maxhmmpf >= 50000 && maxn >= 50000);
-    /* (wide beams keep the round-3 SWEEP in the resolve launch, whose workgroups G_RES_MANY was never meant to size: 128 there, as
-     * before the list-position grids were retuned -- configs[4]: 363 us per launch against 659) */
-    if (ud->big_wl && O.g_res <= 0 && n_lanes >= ud->many) ud->g_res = max(1, min((proto->N + RSBLOCK - 1) / RSBLOCK, 128));
-    if (ud->hist_possible && -cfg->hmmbeam / NBIN == 0) {
+    if (ud->geom.hist_possible && -cfg->hmmbeam / NBIN == 0) {
         s3a_set_error("s3a_uttdec_init: -beam too narrow for histogram pruning (bin width 0)");
         goto fail;
     }
@@ -3895,22 +3852,8 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
         P.lcmap = ud->d_lcmap;
     }
 
-    /* look-ahead scoring (ku_score_window): the 39/40-dimensional case with a 16-bit log-add table and at most 64
-     * Gaussian slots per senone; K = 8 frames per window: from 128 lanes on that is the ~1024 (lane, frame) slots a model pass
-     * amortises over, and with fewer lanes a longer window buys < 1 % (measured: one lane 94.6 x real time with K = 64, 93.5
-     * with 8; 8 and 32 lanes: no difference) while a refilled lane has to wait for a window boundary.  opts->window_max > 0:
-     * up to that many frames so that a pass has ~1024 slots; opts->window: exactly that (0: the per-frame scoring kernels). */
-    {
-        int32_t K = 0;
-        if (d->D4 == D4MAIN && d->CP <= 64 && d->Gpad % 512 == 0) {
-            K = 8;
-            if (O.window_max > 8) K = min(((O.window_max + 7) / 8) * 8, max(8, (((1024 + n_lanes - 1) / n_lanes + 7) / 8) * 8));
-            if (O.window >= 0) K = (O.window + 7) / 8 * 8;
-        }
-        S.win_K = K;
-        ud->times = O.times;
-        ud->win_fpc = O.window_fpc;
-    }
+    S.win_K = ud->geom.win_K;       /* (look-ahead scoring: ku_score_window) */
+    ud->times = O.times;
     ud->lane.resize(n_lanes);
     for (auto &hl : ud->lane) memset((void *)&hl, 0, sizeof hl);
     if (T > WL_MAXT) { s3a_set_error("s3a_uttdec_init: more than %d lextrees", WL_MAXT); goto fail; }
@@ -3919,11 +3862,8 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
     DM(ud->mem, ud->d_fgbase, 64);
     if (hipMemset(ud->d_fgbase, 0, 64) != hipSuccess) goto fail;
     ud->S.fgbase = ud->d_fgbase;
-    ud->use_graph = O.graph != 0 && !ud->big_wl && !O.framecheck;
-    ud->persist = O.persist >= 0 && !ud->use_graph && !O.framecheck ? (O.persist > 1 ? 3 : O.persist > 0 ? 2 : 1) : 0;     /* (2: whatever the lane count; 3: and with the general barrier only) */
-    ud->kf_cluster_opt = O.cluster;
     ud->sb_rows_max = O.score_rows_max > 0 ? (size_t)O.score_rows_max : 0;
-    if (ud->persist) {
+    if (ud->geom.persist) {
         DM(ud->mem, ud->d_kfnext, (size_t)(KFN_LANE + n_lanes) * 4);
         DM(ud->mem, ud->d_kfargs, sizeof(KfArgs) * KF_ARG_SLOTS);
         if (!ud->mem.pin(ud->h_kfargs, sizeof(KfArgs) * KF_ARG_SLOTS)) { s3a_set_error("s3a_uttdec_init: pinned allocation failed"); goto fail; }
@@ -3933,7 +3873,6 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
         DM(ud->mem, ud->d_kfleft, (size_t)3 * n_lanes * 4);
         if (ud->device >= 0 && ud->device < 64) { g_kf_live[ud->device]++; ud->kf_counted = 1; ud->kf_shared = kf_device_lock(ud->device) ? 0 : 1; }
     }
-    ud->scan_small_from = O.scan_small_from > 0 ? O.scan_small_from : 64;
     ud->hyp_wcap = max_frames + 4;
     if (!ud->mem.pin(ud->h_ctx_up, sizeof(UCtx) * n_lanes) || !ud->mem.pin(ud->h_ctx_dn, sizeof(UCtx) * n_lanes)
         || !ud->mem.pin(ud->h_hyp_hdr, ((size_t)n_lanes * UH_N + 1) * 4) || !ud->mem.pin(ud->h_hyp_words, (size_t)n_lanes * ud->hyp_wcap * 6 * 4)) { s3a_set_error("s3a_uttdec_init: pinned allocation failed"); goto fail; }
@@ -3948,7 +3887,7 @@ s3a_uttdec_init_opts(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g, const in
         hl.sc = s3a_scorer_init_private(g, cd2cisen, n_sen, n_ci_sen, ds_ratio, cond_ds, ci_pbeam, tighten_factor, max_cd);
         if (!hl.ls || !hl.sc) goto fail;
         if (z == 0) {
-            S.gp_n = hl.sc->gp_n;
+            S.gp_n = ud->shape.gp_n = hl.sc->gp_n;
             S.ci_pbeam = hl.sc->ci_pbeam;
             S.ci_pbeam_tight = (int32_t)((float)hl.sc->ci_pbeam * hl.sc->tighten_factor);
             S.max_cd = max_cd; S.tighten = hl.sc->tighten_factor;
@@ -4093,103 +4032,77 @@ lane_begin(s3a_uttdec_t *ud, int32_t z, const float *feat, int32_t nfr, int32_t 
     return S3A_OK;
 }
 
-/* ---- look-ahead scoring: geometry + launch of ku_score_window ---- */
-struct UwGeom { int32_t nt, fpc, n_chunks, n_tiles, grid, tab_lds; size_t lds; };
+/* ---- the launch geometry as the engine holds it (s3a_uttgeom.h has the rules) ---- */
+static_assert(UGC_DBLOCK == DBLOCK && UGC_RSBLOCK == RSBLOCK && UGC_M3BLOCK == M3BLOCK && UGC_SCAN_THREADS == SCAN_THREADS && UGC_UR_K == UR_K
+              && UGC_UW_FB == UW_FB && UGC_USEL_G == USEL_G && UGC_UG_FB == UG_FB && UGC_UG_MAX == UG_MAX && UGC_WL_THREADS == WL_THREADS
+              && UGC_WL_MAXT == WL_MAXT && UGC_WL_MAXCALL == WL_MAXCALL && UGC_WL_BIG_G == WL_BIG_G && UGC_UE_WG_PER_TREE == UE_WG_PER_TREE
+              && UGC_KF_MAXC == KF_MAXC && UGC_KF_SENBITS == KF_SENBITS && UGC_KF_STAGES == KF_STAGES && UGC_KF_LEAD == KF_OVERLAP_LEAD
+              && UGC_PIECE == KFP_PIECE && UGC_D4MAIN == D4MAIN && UGC_EVBLOCK_LONG_LIST == EVBLOCK_LONG_LIST
+              && UGC_SCAN_LONG_LIST == SCAN_LONG_LIST && UGC_UWGROUP_BYTES == sizeof(UwGroup) && KF_NT == WL_THREADS,
+              "s3a_uttgeom.h's copies are the kernels' constants");
 
-static size_t
-uw_lds_bytes(int32_t fpc, int32_t nt, bool tab_lds, uint32_t tab_size)
+/* the ku_frames instantiation this engine launches: the launch, the occupancy query and the static-LDS query all ask here */
+typedef void (*kf_kernel_t)(const ULane *, const KfArgs *, int32_t, int32_t, int32_t *, int32_t, int32_t);
+static kf_kernel_t
+kf_kernel(const s3a_uttdec_t *ud)
 {
-    size_t b = (size_t)fpc * D4MAIN * 4 * sizeof(float);
-    b += (size_t)(nt / 64) * UW_FB * 65 * sizeof(int32_t);
-    b = (b + 15) & ~(size_t)15;
-    b += (size_t)(fpc / UW_FB) * sizeof(UwGroup);
-    b = (b + 15) & ~(size_t)15;
-    if (tab_lds) b += ((size_t)tab_size * 2 + 15) & ~(size_t)15;
-    return b;
+    const bool heur = ud->shape.pheurtype > 0;          /* (call_facts: the engine's, as of this call -- the copy the route's rules read) */
+    if (ud->S.ne == 5) return ud->exact ? (heur ? ku_frames<5, true, true> : ku_frames<5, true, false>) : (heur ? ku_frames<5, false, true> : ku_frames<5, false, false>);
+    return ud->exact ? (heur ? ku_frames<3, true, true> : ku_frames<3, true, false>) : (heur ? ku_frames<3, false, true> : ku_frames<3, false, false>);
 }
 
-/* (lane, frame) slots per chunk: a workgroup needs ~100 KB of LDS, so one is resident per CU and the grid runs in rounds
- * of n_cu workgroups; time ~ rounds x (slots per chunk + a start-up worth ~10 slots): s3a_device.hip, pick_fpc */
-static UwGeom
-uw_geometry(const s3a_uttdec_t *ud, int32_t n_lanes, int32_t total_slots = 0)
+/* is this engine free to size clusters for the whole device?  (alone in its process AND no other process holds the device's lock) */
+static bool
+kf_alone(const s3a_uttdec_t *ud)
 {
-    const UShared &S = ud->S;
-    const int32_t total = total_slots > 0 ? total_slots : n_lanes * S.win_K, n_cu = max(1, ud->g->dev->n_cu);
-    UwGeom q;
-    q.tab_lds = total >= 2 * UW_FB ? 1 : 0;
-    q.nt = q.tab_lds ? 512 : 256;
-    q.n_tiles = S.Gpad / q.nt;
-    int32_t best_fpc = UW_FB;
-    int64_t best_cost = -1;
-    for (int32_t nc = 1; nc <= 512; nc++) {
-        int32_t fpc = (total + nc - 1) / nc;
-        fpc = ((fpc + UW_FB - 1) / UW_FB) * UW_FB;
-        if (fpc > 256) continue;
-        const int32_t chunks = (total + fpc - 1) / fpc;
-        const int64_t rounds = ((int64_t)q.n_tiles * chunks + n_cu - 1) / n_cu;
-        const int64_t cost = rounds * (fpc + 10);
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_fpc = fpc; }
-        if (fpc <= UW_FB) break;
+    return ud->device >= 0 && ud->device < 64 && g_kf_live[ud->device].load() <= 1 && !ud->kf_shared;
+}
+
+/* what a call adds to the shape (ud->call, for every step of the call): its kind and size, whether the engine is alone (sampled again
+ * wherever a cluster size is chosen: kf_launch_chain, enqueue_block), the variants in force.  The shape's own -pheurtype is brought up to date here
+ * (s3a_uttdec_enable_pheur switches it on AND off), and with it, whenever the ku_frames instantiation to launch is another than the one
+ * last asked, that kernel's own figures: the workgroups the device holds at once (a cluster's workgroups wait for one another) and its
+ * static LDS (what the companion scoring shape may take beside it) */
+static void
+call_facts(s3a_uttdec_t *ud, bool queue, int32_t n_utt)
+{
+    const s3a_variants_t *va = s3a_variants();
+    UgCall &c = ud->call;
+    memset(&c, 0, sizeof c);
+    c.queue = queue; c.n_utt = n_utt; c.alone = kf_alone(ud); c.prof_every = ud->prof_every; c.second_pass = ud->dag != NULL; c.keep_lat = ud->q_keep_lat;
+    c.hist_sort_launch = va->hist_sort_launch; c.kf_no_relay = va->kf_no_relay; c.kf_relay_at = va->kf_relay_at; c.kf_no_overlap = va->kf_no_overlap;
+    c.kf_overlap_n1 = va->kf_overlap_n1; c.kf_overlap_lead = va->kf_overlap_lead; c.kf_overlap_round = va->kf_overlap_round;
+    UgShape &s = ud->shape;
+    s.pheurtype = ud->S.pheurtype;
+    if (ud->geom.persist && ud->kf_asked != (const void *)kf_kernel(ud)) {
+        int nb = 0;
+        ud->kf_asked = (const void *)kf_kernel(ud);
+        hipFuncAttributes fa;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf_kernel(ud), KF_NT, 0) != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = 1; }
+        s.kf_slots = nb * s.n_cu;
+        if (hipFuncGetAttributes(&fa, (const void *)kf_kernel(ud)) != hipSuccess) { (void)hipGetLastError(); s.kf_lds = 0; }
+        else s.kf_lds = (int32_t)fa.sharedSizeBytes;
     }
-    if (ud->win_fpc > 0) best_fpc = min(256, ((ud->win_fpc + UW_FB - 1) / UW_FB) * UW_FB);
-    q.fpc = best_fpc;
-    q.n_chunks = (total + q.fpc - 1) / q.fpc;
-    q.grid = ((q.n_tiles + 7) / 8) * q.n_chunks * 8;
-    q.lds = uw_lds_bytes(q.fpc, q.nt, q.tab_lds != 0, S.tab_size);
-    if (q.lds > 160 * 1024) { q.tab_lds = 0; q.lds = uw_lds_bytes(q.fpc, q.nt, false, S.tab_size); }
-    return q;
 }
 
-/* THE COMPANION SHAPE: a scoring workgroup that fits a CU BESIDE one ku_frames workgroup (kf_decode_queue scores the later utterances
- * of a queue while the first ones are searched).  256 threads at no more than 256 VGPRs are one wave per SIMD beside the search's two of
- * 128; the LDS is what the CU has left beside the search's workgroup, by the kernels' own figures (ku_frames' static LDS rounded up to the
- * allocation granule, 1 280 B on a 160 KB CU -- and to 512 B, the older parts', whichever leaves less): the log-add table, the
- * transposition tile and as many frames per chunk as still fit (at most 88).  Same body, same rows as every other shape. */
-#define UW_COMP_FPC_MAX 88
-template <int NE, bool EXACT>
-static int32_t
-kf_static_lds(void)
+/* a frame's launches and the window's scoring pass for n lanes: made when a call first has that many, as graph_for's graphs are */
+static const s3a_uttdec_s::FrameGeom &
+frame_geom(s3a_uttdec_t *ud, int32_t n)
 {
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, (const void *)ku_frames<NE, EXACT>) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return (int32_t)fa.sharedSizeBytes;
-}
-static int32_t
-uw_companion_lds(s3a_uttdec_t *ud)
-{
-    if (ud->kf_comp_lds == 0) {
-        const int32_t cu_lds = 160 * 1024;
-        int32_t lane = ud->S.ne == 5 ? (ud->exact ? kf_static_lds<5, true>() : kf_static_lds<5, false>())
-                                     : (ud->exact ? kf_static_lds<3, true>() : kf_static_lds<3, false>());
-        if (lane <= 0 || lane > cu_lds / 2) lane = cu_lds / 2;
-        const int32_t left = cu_lds - max((lane + 1279) / 1280 * 1280, (lane + 511) / 512 * 512);
-        ud->kf_comp_lds = left / 1280 * 1280;
-    }
-    return ud->kf_comp_lds;
-}
-static UwGeom
-uw_geometry_companion(s3a_uttdec_t *ud, int32_t total_slots)
-{
-    const UShared &S = ud->S;
-    const int32_t room = uw_companion_lds(ud);
-    UwGeom q;
-    q.nt = 256; q.tab_lds = 1;
-    q.n_tiles = S.Gpad / q.nt;
-    q.fpc = min(UW_COMP_FPC_MAX, ((total_slots + UW_FB - 1) / UW_FB) * UW_FB);
-    while (q.fpc > UW_FB && uw_lds_bytes(q.fpc, q.nt, true, S.tab_size) > (size_t)room) q.fpc -= UW_FB;
-    if (uw_lds_bytes(q.fpc, q.nt, true, S.tab_size) > (size_t)room) {       /* (a table that does not fit beside the search stays in memory) */
-        q.tab_lds = 0;
-        q.fpc = min(UW_COMP_FPC_MAX, ((total_slots + UW_FB - 1) / UW_FB) * UW_FB);
-    }
-    q.n_chunks = (total_slots + q.fpc - 1) / q.fpc;
-    q.grid = ((q.n_tiles + 7) / 8) * q.n_chunks * 8;
-    q.lds = uw_lds_bytes(q.fpc, q.nt, q.tab_lds != 0, S.tab_size);
-    return q;
+    for (const auto &g : ud->frame_geoms)
+        if (g.n == n && g.hist_sort_launch == ud->call.hist_sort_launch) return g;
+    s3a_uttdec_s::FrameGeom g;
+    g.n = n; g.hist_sort_launch = ud->call.hist_sort_launch;
+    g.fr = ug_frame(ud->shape, ud->geom, n, g.hist_sort_launch);
+    g.win = ug_score(ud->shape, ug_window_slots(ud->geom, n));
+    ud->frame_geoms.push_back(g);
+    return ud->frame_geoms.back();
 }
 
+/* ---- look-ahead scoring: launch of ku_score_window ---- */
 template <int CP, bool EXACT>
 static hipError_t
-uw_launch_cp(const s3a_uttdec_t *ud, const UwGeom &q, int32_t n, int32_t f0, hipStream_t st, bool attr_only, const UwGroup *gdesc = NULL, int32_t n_g = 0)
+uw_launch_cp(const s3a_uttdec_t *ud, const UgScore &q, int32_t n, int32_t f0, hipStream_t st, bool attr_only, const UwGroup *gdesc = NULL, int32_t n_g = 0)
 {
     /* (attr_only: the function attribute alone -- before a stream capture, where it may not be set) */
 #define UW_GO(TAB, NT) do { auto kern = ku_score_window<CP, EXACT, TAB, NT>;                                            \
@@ -4210,7 +4123,7 @@ uw_launch(s3a_uttdec_t *ud, int32_t n, int32_t f0, bool attr_only = false, const
 {
     /* (gdesc: n_g groups of 8 frames from the host's table instead of the lanes' windows; companion: the shape that fits beside the search;
      * st: the stream, the engine's unless given) */
-    const UwGeom q = companion && gdesc ? uw_geometry_companion(ud, n_g * UW_FB) : uw_geometry(ud, n, gdesc ? n_g * UW_FB : 0);
+    const UgScore q = !gdesc ? frame_geom(ud, n).win : companion ? ug_companion(ud->shape, n_g * UW_FB) : ug_score(ud->shape, n_g * UW_FB);
     if (!st) st = ud->stream;
     hipError_t e;
 #define UW_CASE(cp) case cp: e = ud->exact ? uw_launch_cp<cp, true>(ud, q, n, f0, st, attr_only, gdesc, n_g) : uw_launch_cp<cp, false>(ud, q, n, f0, st, attr_only, gdesc, n_g); break
@@ -4229,27 +4142,26 @@ enum { UK_ENTER1, UK_ENTER2, UK_ENTER3, UK_GATED_CI, UK_GATED_CD, UK_COMSEN, UK_
 static const char *const uk_names[UK_N] = { "ku_enter1", "ku_enter2", "ku_enter3_mark", "ku_gated_ci", "ku_gated_cd",
     "ku_comsen_max", "ku_hmm_eval", "ku_hist_count", "ku_hist_sort", "ku_weak", "ku_resolve", "ku_scan", "ku_emit", "ku_emit_word", "ku_wl_p2", "ku_wl_p3", "ku_wl_p4ab", "ku_wl_p5", "ku_wl_finish", "ku_score_window" };
 
+/* frame f of lanes 0 .. G.n - 1 as launches: every grid and every variant is G's (frame_geom) or the engine's (ud->geom); the ladders
+ * below only pick the template instantiation a record names */
 static int32_t
-enqueue_frame(s3a_uttdec_t *ud, int32_t n, int32_t f, bool prof)
+enqueue_frame(s3a_uttdec_t *ud, const UgFrame &G, int32_t f, bool prof)
 {
     hipStream_t st = ud->stream;
     const ULane *LN = ud->d_lanes;
     const UShared &S = ud->S;
-    const int32_t T = S.T;
+    const UgEngine &E = ud->geom;
+    const int32_t T = S.T, n = G.n;
+    const bool heur = S.pheurtype > 0;
     /* profiled frames bracket every launch with HIP events on the launch stream */
 #define UKL(cls, ...) do { hipEvent_t a_ = NULL, b_ = NULL;                                                   \
         if (prof) { (void)hipEventCreate(&a_); (void)hipEventCreate(&b_); (void)hipEventRecord(a_, st); }        \
         hipLaunchKernelGGL(__VA_ARGS__);                                                                         \
         if (prof) { (void)hipEventRecord(b_, st); ud->prof_ev.push_back({ cls, a_, b_ }); } } while (0)
-    UKL(UK_ENTER1, ku_enter1, dim3(ud->g_ent, 1, n), dim3(256), 0, st, LN, S, f);
-    /* (from 64 lanes on: 256-thread workgroups, as the scan below: 365 -> 371 k frames/s with four engines on the chip) */
-    if (n >= ud->scan_small_from)
-        UKL(UK_ENTER2, ku_enter2<256>, dim3(G_ENTER2_MANY, 1, n), dim3(256), 0, st, LN, S, f);
-    else
-        UKL(UK_ENTER2, ku_enter2<SCAN_THREADS>, dim3(n >= ud->many ? 12 : WL_MAXCALL, 1, n), dim3(SCAN_THREADS), 0, st, LN, S, f);
-    UKL(UK_ENTER3, ku_enter3_mark, dim3(ud->g_mark, 1, n), dim3(M3BLOCK), 0, st, LN, S, f);
-    const int32_t g_ci = (S.n_ci_sen * S.CP + 255) / 256, g_cd = ((S.n_sen - S.n_ci_sen) * S.CP + 255) / 256;
-    const int32_t g_cs = (S.n_cs + 255) / 256;         /* composite senones: a wave looks at 64 */
+    UKL(UK_ENTER1, ku_enter1, dim3(E.g_ent, 1, n), dim3(256), 0, st, LN, S, f);
+    if (G.enter2_threads == 256) UKL(UK_ENTER2, ku_enter2<256>, dim3(G.g_enter2, 1, n), dim3(256), 0, st, LN, S, f);
+    else UKL(UK_ENTER2, ku_enter2<SCAN_THREADS>, dim3(G.g_enter2, 1, n), dim3(SCAN_THREADS), 0, st, LN, S, f);
+    UKL(UK_ENTER3, ku_enter3_mark, dim3(E.g_mark, 1, n), dim3(M3BLOCK), 0, st, LN, S, f);
     if (S.win_K > 0) {
         /* look-ahead scoring: every K frames one pass over the model for all lanes' coming K frames; per frame the
          * composite senones' members join the mask and the gate selects (ku_select) */
@@ -4260,95 +4172,58 @@ enqueue_frame(s3a_uttdec_t *ud, int32_t n, int32_t f, bool prof)
             if (rc != S3A_OK) return rc;
             if (prof) { (void)hipEventRecord(b_, st); ud->prof_ev.push_back({ UK_WINDOW, a_, b_ }); }
         }
-        if (g_cs) UKL(UK_GATED_CI, ku_comsen_mark, dim3(g_cs, 1, n), dim3(256), 0, st, LN, S, f);
-        if (S.max_cd < S.n_sen - S.n_ci_sen) UKL(UK_GATED_CI, ku_dyn_ci_beam, dim3(1, 1, n), dim3(1024), 0, st, LN, S, f);
-        const int32_t g_sel = max(1, min(USEL_G, min(S.gp_n, (S.n_sen - S.n_ci_sen + 255) / 256)));
-        if (ud->exact) UKL(UK_GATED_CD, ku_select<true>, dim3(g_sel, 1, n), dim3(256), 0, st, LN, S, f, S.win_K);
-        else UKL(UK_GATED_CD, ku_select<false>, dim3(g_sel, 1, n), dim3(256), 0, st, LN, S, f, S.win_K);
+        if (G.g_cs) UKL(UK_GATED_CI, ku_comsen_mark, dim3(G.g_cs, 1, n), dim3(256), 0, st, LN, S, f);
+        if (G.dyn_ci) UKL(UK_GATED_CI, ku_dyn_ci_beam, dim3(1, 1, n), dim3(1024), 0, st, LN, S, f);
+        if (ud->exact) UKL(UK_GATED_CD, ku_select<true>, dim3(G.g_sel, 1, n), dim3(256), 0, st, LN, S, f, S.win_K);
+        else UKL(UK_GATED_CD, ku_select<false>, dim3(G.g_sel, 1, n), dim3(256), 0, st, LN, S, f, S.win_K);
     }
     else {
-    /* from UG_FB lanes on the CD senones of all lanes are ONE pass over the model (39/40-dimensional features,
-     * >= UG_FB Gaussian slots per senone); (S3A_UTT_NO_MULTI: the per-lane kernel whatever the lane count -- tests) */
-    const bool multi = n >= UG_FB && S.D4 == D4MAIN && S.CP >= UG_FB && S.CP <= 64 && g_cd > 0 && S.gp_n == g_cd
-        && !ud->no_multi;
-    const int32_t gz = (n + UG_MAX - 1) / UG_MAX, groups = (min(n, UG_MAX) + UG_FB - 1) / UG_FB;
-    const int32_t gy_env = ud->gy;
-    const dim3 gm(g_cd, gy_env > 0 ? min(groups, gy_env) : max(1, min(groups, 2 * ud->g->dev->n_cu / max(1, g_cd * gz))), gz);
-    if (ud->exact) {
-        if (g_ci) UKL(UK_GATED_CI, (ku_gated<true, true>), dim3(g_ci + g_cs, 1, n), dim3(256), 0, st, LN, S, f);
-        if (S.max_cd < S.n_sen - S.n_ci_sen) UKL(UK_GATED_CI, ku_dyn_ci_beam, dim3(1, 1, n), dim3(1024), 0, st, LN, S, f);
-        if (multi) UKL(UK_GATED_CD, (ku_gated_cd_multi<true>), gm, dim3(256), 0, st, LN, S, n, f);
-        else if (g_cd) UKL(UK_GATED_CD, (ku_gated<true, false>), dim3(g_cd, 1, n), dim3(256), 0, st, LN, S, f);
+        /* the per-frame gated kernels; G.multi: the CD senones of all lanes as ONE pass over the model */
+        const dim3 gm(G.gm_x, G.gm_y, G.gm_z);
+        if (ud->exact) {
+            if (G.g_ci) UKL(UK_GATED_CI, (ku_gated<true, true>), dim3(G.g_ci + G.g_cs, 1, n), dim3(256), 0, st, LN, S, f);
+            if (G.dyn_ci) UKL(UK_GATED_CI, ku_dyn_ci_beam, dim3(1, 1, n), dim3(1024), 0, st, LN, S, f);
+            if (G.multi) UKL(UK_GATED_CD, (ku_gated_cd_multi<true>), gm, dim3(256), 0, st, LN, S, n, f);
+            else if (G.g_cd) UKL(UK_GATED_CD, (ku_gated<true, false>), dim3(G.g_cd, 1, n), dim3(256), 0, st, LN, S, f);
+        }
+        else {
+            if (G.g_ci) UKL(UK_GATED_CI, (ku_gated<false, true>), dim3(G.g_ci + G.g_cs, 1, n), dim3(256), 0, st, LN, S, f);
+            if (G.dyn_ci) UKL(UK_GATED_CI, ku_dyn_ci_beam, dim3(1, 1, n), dim3(1024), 0, st, LN, S, f);
+            if (G.multi) UKL(UK_GATED_CD, (ku_gated_cd_multi<false>), gm, dim3(256), 0, st, LN, S, n, f);
+            else if (G.g_cd) UKL(UK_GATED_CD, (ku_gated<false, false>), dim3(G.g_cd, 1, n), dim3(256), 0, st, LN, S, f);
+        }
     }
-    else {
-        if (g_ci) UKL(UK_GATED_CI, (ku_gated<false, true>), dim3(g_ci + g_cs, 1, n), dim3(256), 0, st, LN, S, f);
-        if (S.max_cd < S.n_sen - S.n_ci_sen) UKL(UK_GATED_CI, ku_dyn_ci_beam, dim3(1, 1, n), dim3(1024), 0, st, LN, S, f);
-        if (multi) UKL(UK_GATED_CD, (ku_gated_cd_multi<false>), gm, dim3(256), 0, st, LN, S, n, f);
-        else if (g_cd) UKL(UK_GATED_CD, (ku_gated<false, false>), dim3(g_cd, 1, n), dim3(256), 0, st, LN, S, f);
-    }
-    }
-    if (g_cs) UKL(UK_COMSEN, ku_comsen_max, dim3(g_cs, 1, n), dim3(256), 0, st, LN, S, f);
+    if (G.g_cs) UKL(UK_COMSEN, ku_comsen_max, dim3(G.g_cs, 1, n), dim3(256), 0, st, LN, S, f);
     if (S.ne == 5) {
-        if (ud->eval_block == 256) UKL(UK_HMM_EVAL, (ku_hmm_eval<256, 5>), dim3(ud->g_eval, T, n), dim3(256), 0, st, LN, S, f);
-        else UKL(UK_HMM_EVAL, (ku_hmm_eval<64, 5>), dim3(ud->g_eval, T, n), dim3(64), 0, st, LN, S, f);
+        if (E.eval_block == 256) UKL(UK_HMM_EVAL, (ku_hmm_eval<256, 5>), dim3(E.g_eval, T, n), dim3(256), 0, st, LN, S, f);
+        else UKL(UK_HMM_EVAL, (ku_hmm_eval<64, 5>), dim3(E.g_eval, T, n), dim3(64), 0, st, LN, S, f);
     }
-    else if (ud->eval_block == 256)
-        UKL(UK_HMM_EVAL, (ku_hmm_eval<256, 3>), dim3(ud->g_eval, T, n), dim3(256), 0, st, LN, S, f);
+    else if (E.eval_block == 256)
+        UKL(UK_HMM_EVAL, (ku_hmm_eval<256, 3>), dim3(E.g_eval, T, n), dim3(256), 0, st, LN, S, f);
     else
-        UKL(UK_HMM_EVAL, (ku_hmm_eval<64, 3>), dim3(ud->g_eval, T, n), dim3(64), 0, st, LN, S, f);
-    /* the not active nodes from the list of stamped parent sets (the stamping pass then also lists the sets) -- not with wide
-     * beams (tens of thousands of active HMMs, thousands of listed sets per frame: configs[4] is faster with the sweep) */
-    const int32_t by_parents = n >= ud->many && !ud->big_wl && !s3a_variants()->resolve_sweep ? 1 : 0;
-    {
-        /* many lanes: the (rare) histogram sort rides on the count's launch (its 256-thread form is the one used there anyway) */
-        const int32_t own_sort = ud->hist_possible && n >= ud->scan_small_from && !s3a_variants()->hist_sort_launch ? 1 : 0;
-        UKL(UK_HIST_COUNT, ku_hist_count, dim3(max(1, min((S.maxn + DBLOCK - 1) / DBLOCK, n >= ud->many ? G_HIST_MANY : 64)), T, n), dim3(DBLOCK), 0, st, LN, S, f, own_sort, by_parents);
-        if (ud->hist_possible && !own_sort) {
-            /* (from 64 lanes on 256 threads: the launch's 128 workgroups mostly only leave, and small ones find a slot sooner) */
-            if (n >= ud->scan_small_from) UKL(UK_HIST_SORT, ku_hist_sort<256>, dim3(1, 1, n), dim3(256), 0, st, LN, S, f, by_parents);
-            else UKL(UK_HIST_SORT, ku_hist_sort<SCAN_THREADS>, dim3(1, 1, n), dim3(SCAN_THREADS), 0, st, LN, S, f, by_parents);
-        }
+        UKL(UK_HMM_EVAL, (ku_hmm_eval<64, 3>), dim3(E.g_eval, T, n), dim3(64), 0, st, LN, S, f);
+    UKL(UK_HIST_COUNT, ku_hist_count, dim3(G.g_hist, T, n), dim3(DBLOCK), 0, st, LN, S, f, G.own_sort, G.by_parents);
+    if (E.hist_possible && !G.own_sort) {
+        if (G.sort_threads == 256) UKL(UK_HIST_SORT, ku_hist_sort<256>, dim3(1, 1, n), dim3(256), 0, st, LN, S, f, G.by_parents);
+        else UKL(UK_HIST_SORT, ku_hist_sort<SCAN_THREADS>, dim3(1, 1, n), dim3(SCAN_THREADS), 0, st, LN, S, f, G.by_parents);
     }
-    if (ud->weak_possible && S.pheurtype > 0) UKL(UK_WEAK, ku_weak_heur, dim3(T, 1, n), dim3(1024), 0, st, LN, S, f);
+    if (E.weak_possible && heur) UKL(UK_WEAK, ku_weak_heur, dim3(T, 1, n), dim3(1024), 0, st, LN, S, f);
     else {
-        if (ud->weak_possible) UKL(UK_WEAK, ku_weak, dim3(1, 1, n), dim3(SCAN_THREADS), 0, st, LN, S, f);
-        if (S.pheurtype > 0) UKL(UK_RESOLVE, ku_heur_thresh, dim3(T, 1, n), dim3(1024), 0, st, LN, S, f);
+        if (E.weak_possible) UKL(UK_WEAK, ku_weak, dim3(1, 1, n), dim3(SCAN_THREADS), 0, st, LN, S, f);
+        if (heur) UKL(UK_RESOLVE, ku_heur_thresh, dim3(T, 1, n), dim3(1024), 0, st, LN, S, f);
     }
-    {   /* (the active HMMs by list position: ud->g_res workgroups that loop; the rest: a sweep, UR_K nodes per thread) */
-        const int32_t GB = ((S.N + UR_K - 1) / UR_K + RSBLOCK - 1) / RSBLOCK;
-        if (by_parents) {
-            if (S.pheurtype > 0) UKL(UK_RESOLVE, ku_resolve_plist<true>, dim3(ud->g_res + UR_GL, 1, n), dim3(RSBLOCK), 0, st, LN, S, f);
-            else UKL(UK_RESOLVE, ku_resolve_plist<false>, dim3(ud->g_res + UR_GL, 1, n), dim3(RSBLOCK), 0, st, LN, S, f);
-        }
-        else if (S.pheurtype > 0) {
-            if (n >= ud->many) UKL(UK_RESOLVE, ku_resolve_lists<true>, dim3(ud->g_res + GB, 1, n), dim3(RSBLOCK), 0, st, LN, S, f);
-            else UKL(UK_RESOLVE, ku_resolve<true>, dim3((S.N + RSBLOCK - 1) / RSBLOCK, 1, n), dim3(RSBLOCK), 0, st, LN, S, f);
-        }
-        else if (n >= ud->many && ud->urk == 16) { const int32_t GB16 = ((S.N + 15) / 16 + RSBLOCK - 1) / RSBLOCK; UKL(UK_RESOLVE, (ku_resolve_lists<false, 16>), dim3(ud->g_res + GB16, 1, n), dim3(RSBLOCK), 0, st, LN, S, f); }
-        else if (n >= ud->many && ud->urk == 4) { const int32_t GB4 = ((S.N + 3) / 4 + RSBLOCK - 1) / RSBLOCK; UKL(UK_RESOLVE, (ku_resolve_lists<false, 4>), dim3(ud->g_res + GB4, 1, n), dim3(RSBLOCK), 0, st, LN, S, f); }
-        else if (n >= ud->many) UKL(UK_RESOLVE, ku_resolve_lists<false>, dim3(ud->g_res + GB, 1, n), dim3(RSBLOCK), 0, st, LN, S, f);
-        else UKL(UK_RESOLVE, ku_resolve<false>, dim3((S.N + RSBLOCK - 1) / RSBLOCK, 1, n), dim3(RSBLOCK), 0, st, LN, S, f);
+    {
+        const dim3 gr(G.g_resolve, 1, n), tr(RSBLOCK);
+        if (G.resolve == UG_RES_PLIST) { if (heur) UKL(UK_RESOLVE, ku_resolve_plist<true>, gr, tr, 0, st, LN, S, f); else UKL(UK_RESOLVE, ku_resolve_plist<false>, gr, tr, 0, st, LN, S, f); }
+        else if (G.resolve == UG_RES_LISTS) { if (heur) UKL(UK_RESOLVE, ku_resolve_lists<true>, gr, tr, 0, st, LN, S, f); else UKL(UK_RESOLVE, ku_resolve_lists<false>, gr, tr, 0, st, LN, S, f); }
+        else if (heur) UKL(UK_RESOLVE, ku_resolve<true>, gr, tr, 0, st, LN, S, f);
+        else UKL(UK_RESOLVE, ku_resolve<false>, gr, tr, 0, st, LN, S, f);
     }
-    /* the scan over long lists: either one workgroup per possible chunk, chained (a chunk waits for chunks with SMALLER
-     * numbers only = workgroups dispatched before it: the wait ends whatever else runs on the chip), when that is no more
-     * workgroups than the chip holds -- a single lane, wide beams --, or one workgroup per tree that walks the chunks itself.
-     * (Round 2 had a few workgroups per tree taking the chunks in turn: workgroup 0's second chunk then waits for the LAST
-     * workgroup's first, a workgroup dispatched after it -- with several engines on the chip every slot can end up held by
-     * such a waiter whose partner is not dispatched yet: observed as WL_E_SCAN time-outs with 8 engines of 64 lanes;
-     * opts->scan_g still asks for that variant.) */
-    const int32_t scan_gc = ud->scan_gc > 0 ? min(ud->scan_gc, ud->scan_nc) : ((long long)T * n * ud->scan_nc <= 768 ? ud->scan_nc : 1);
-    /* (one workgroup per tree: it walks the chunks with the totals in a register -- no flags, no look-back) */
-    /* (from 64 lanes on, one workgroup per tree: 256 threads -- four times the chunks to walk, 53 instead of 29 us per 128-lane
-     * launch alone, but with four engines on the chip a 256-thread workgroup finds a slot where a 1024-thread one waits for half
-     * a CU: 355 -> 362 k frames/s; with 32-lane engines the other way round: 268 -> 259 k) */
-    if (scan_gc == 1 && n >= ud->scan_small_from)
-        UKL(UK_SCAN, ku_scan<256>, dim3(T, 1, n), dim3(256), 0, st, LN, S, 1, 1, f);
-    else
-        UKL(UK_SCAN, ku_scan<SCAN_THREADS>, dim3(T * scan_gc, 1, n), dim3(SCAN_THREADS), 0, st, LN, S, scan_gc == 1 ? 1 : ud->scan_nc, scan_gc, f);
-    /* (many lanes: fewer emission workgroups per tree -- each sweeps further -- instead of thousands of idle ones) */
-    UKL(UK_WORD, ku_emit_word, dim3(1 + (n >= ud->many && !ud->big_wl ? 1024 / WL_THREADS : UE_WG_PER_TREE) * T, 1, n), dim3(WL_THREADS), 0, st, LN, S, ud->lm->d, ud->dict, ud->par, f, ud->big_wl);
-    if (ud->big_wl) {
-        const dim3 gb(WL_BIG_G, 1, n), one(1, 1, n), tb(WL_THREADS);
+    if (G.scan_threads == 256) UKL(UK_SCAN, ku_scan<256>, dim3(G.g_scan, 1, n), dim3(256), 0, st, LN, S, 1, 1, f);
+    else UKL(UK_SCAN, ku_scan<SCAN_THREADS>, dim3(G.g_scan, 1, n), dim3(SCAN_THREADS), 0, st, LN, S, G.scan_nc_arg, G.scan_gc, f);
+    UKL(UK_WORD, ku_emit_word, dim3(G.g_emit, 1, n), dim3(WL_THREADS), 0, st, LN, S, ud->lm->d, ud->dict, ud->par, f, E.big_wl);
+    if (G.g_wide) {
+        const dim3 gb(G.g_wide, 1, n), one(1, 1, n), tb(WL_THREADS);
         UKL(UK_WL_P2, ku_wl_p2, gb, tb, 0, st, LN, ud->lm->d, ud->dict, ud->par, f);
         UKL(UK_WL_P3, ku_wl_p3, gb, tb, 0, st, LN, ud->dict, ud->par, f);
         UKL(UK_WL_P4, ku_wl_p4a, gb, tb, 0, st, LN, ud->par, f);
@@ -4374,86 +4249,14 @@ q_reserve(s3a_uttdec_t *ud, s3a_grow<TP> &b, int sides, size_t need, const char 
 }
 
 /* ---- ku_frames: the frames [fg0, fg0 + nf) of all lanes as ONE launch (behind the look-ahead pass that scores them) ---- */
-/* does this engine, as it is configured now, run its frames through ku_frames? */
-/* (n: the lanes the call keeps busy.  Measured with one engine on the hub4-shaped task, ku_frames : launches, k frames/s -- 256 lanes
- * 443 : 288, 128 lanes (clusters of 3) 407 : 223, 64 lanes (4) 273 : 153, 32 lanes (4) 159 : 110, 16 lanes (8) 91 : 73, 8 lanes (8)
- * 54.7 : 45.2, 4 lanes (16) 28.2 : 27.7, one lane (16) 7.6 : 9.4 -- with the clusters' XCD-local barrier (the general one, an L2
- * write-back per workgroup and step: 128 lanes 284, 64 lanes 216, and the launches won below 96 lanes).  Larger clusters do not pay
- * (32 lanes: 159 / 146 / 94 k with 4 / 8 / 15 workgroups; 64 lanes: 273 / 219 k with 4 / 7): the entry ranking and the word level
- * stay one workgroup's.  Below KF_MIN_LANES the launches stay) */
-#define KF_MIN_LANES 8
-#define KF_CLUSTER_MAX(n) ((n) <= 16 ? 8 : 4)
-static bool
-kf_served(const s3a_uttdec_t *ud, int32_t n)
-{
-    const UShared &S = ud->S;
-    /* (a wide-beam engine -- big_wl, configs[4] -- is SERVED, word level and all, but keeps the launches unless asked: 23 000 HMMs and 300 000
-     * word-level candidates per lane-frame want the whole chip per step, not a cluster of 8 workgroups -- 64 lanes: 10.4 k frames/s through
-     * ku_frames against 30.5 k through the launches, 128 lanes 19.4 k : 36.1 k; profiles/r6_experiments.txt 8) */
-    return ud->persist && (ud->persist > 1 || (n >= KF_MIN_LANES && !ud->big_wl)) && S.win_K > 0 && !ud->d_dbg
-        && ud->prof_every == 0 && ((S.ne == 3 && S.nodepk) || S.ne == 5) && S.T <= WL_MAXT && S.n_sen <= KF_SENBITS;
-}
-
-/* workgroups of ku_frames the device holds at once: a cluster's workgroups wait for one another */
-template <int NE, bool EXACT>
-static void
-kf_slots_t(s3a_uttdec_t *ud)
-{
-    if (ud->kf_slots == 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ku_frames<NE, EXACT>, KF_NT, 0) != hipSuccess || nb < 1) nb = 1;
-        ud->kf_slots = nb * ud->g->dev->n_cu;
-    }
-}
-/* ... per XCD, less a margin (the occupancy query can be one workgroup per CU high, MI355X_MICROARCH "Residency") */
-static int32_t
-kf_usable_per_xcd(s3a_uttdec_t *ud)
-{
-    if (ud->kf_slots == 0) {
-        if (ud->S.ne == 5) { if (ud->exact) kf_slots_t<5, true>(ud); else kf_slots_t<5, false>(ud); }
-        else { if (ud->exact) kf_slots_t<3, true>(ud); else kf_slots_t<3, false>(ud); }
-    }
-    const int32_t per_xcd = max(1, ud->kf_slots / 8);
-    return per_xcd - (per_xcd > 8 ? 4 : 0);
-}
-/* is this engine free to size clusters for the whole device?  (alone in its process AND no other process holds the device's lock) */
-static bool
-kf_alone(const s3a_uttdec_t *ud)
-{
-    return ud->device >= 0 && ud->device < 64 && g_kf_live[ud->device].load() <= 1 && !ud->kf_shared;
-}
-/* workgroups per lane for n lanes: the lanes' clusters share the XCDs evenly (lane z on XCD z % 8) and must all be resident */
-static int32_t
-kf_choose_c(s3a_uttdec_t *ud, int32_t n)
-{
-    const int32_t usable = kf_usable_per_xcd(ud), per_xcd = max(1, ud->kf_slots / 8), lanes_per_xcd = (n + 7) / 8;
-    int32_t C = 1;
-    if (ud->kf_cluster_opt > 0) C = ud->kf_cluster_opt;
-    else if (kf_alone(ud)) {
-        const int32_t cmax = ud->big_wl ? 8 : KF_CLUSTER_MAX(n);       /* (wide beams: seven times the HMMs, a word level in chunks) */
-        C = min(per_xcd / lanes_per_xcd, cmax);
-        /* ... but an EVEN fill first: a cluster is as fast as its slowest workgroup, and with one and a half workgroups per CU some share
-         * a CU and some do not -- 128 lanes: 429.5 k frames/s as clusters of 2 (one workgroup per CU) against 406.9 k as clusters of 3
-         * (profiles/r6_experiments.txt 16).  So: as many workgroups per lane as still leave every workgroup a CU of its own, when that is
-         * a cluster at all */
-        const int32_t c1 = min(max(1, ud->g->dev->n_cu / 8) / lanes_per_xcd, cmax);
-        if (c1 >= 2) C = c1;
-    }
-    /* (KF_MAXC: what the kernel's LDS arrays -- the waves' segments, the cluster's scan -- are sized for) */
-    return max(1, min(min(C, KF_MAXC), usable / lanes_per_xcd));
-}
-
+/* (who is served, the cluster sizes, the grids and the relay's stages: ug_kf, s3a_uttgeom.h) */
 /* n: lane slots of the launch (lanes 0 .. n - 1, or -- J.resume -- that many places of the relay's list); C: workgroups per lane; st: the
  * stream (NULL: the engine's) */
-template <int NE, bool EXACT, bool HEUR = false>
 static int32_t
-kf_launch_t(s3a_uttdec_t *ud, int32_t n, const KfJob &J, int32_t C, hipStream_t st)
+kf_launch_c(s3a_uttdec_t *ud, int32_t n, const KfJob &J, int32_t C, hipStream_t st = NULL)
 {
-    auto kern = ku_frames<NE, EXACT, HEUR>;
-    const int32_t lanes_per_xcd = (n + 7) / 8;
     if (!st) st = ud->stream;
     if (!J.resume) ud->kf_last_c = C;
-    const int32_t grid = C == 1 ? n : 8 * C * lanes_per_xcd;
     if (C > 1) HIPCHK(hipMemsetAsync(ud->d_kfbar, 0, (size_t)ud->n_lanes * 8, st));
     /* the launch's shared arguments: a slot of a small ring (pinned + device) so that launches may queue up behind one another */
     if (ud->kf_arg_at > 0 && ud->kf_arg_at % KF_ARG_SLOTS == 0) {
@@ -4464,31 +4267,15 @@ kf_launch_t(s3a_uttdec_t *ud, int32_t n, const KfJob &J, int32_t C, hipStream_t 
     ud->kf_arg_at++;
     ha->S = ud->S; ha->lm = ud->lm->d; ha->dict = ud->dict; ha->par = ud->par; ha->J = J;
     HIPCHK(hipMemcpyAsync(da, ha, sizeof(KfArgs), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(KF_NT), 0, st, ud->d_lanes, (const KfArgs *)da, n, C,
-                       ud->d_kfbar, (ud->weak_possible ? 1 : 0) | (ud->big_wl ? 2 : 0), ud->persist < 3 ? 1 : 0);
-    HIPCHK(hipGetLastError());
+    const ULane *lanes = ud->d_lanes;
+    const KfArgs *A = da;
+    int32_t *bar = ud->d_kfbar, weak = (ud->geom.weak_possible ? 1 : 0) | (ud->geom.big_wl ? 2 : 0), local_ok = ud->geom.persist < 3 ? 1 : 0;
+    void *args[] = { &lanes, &A, &n, &C, &bar, &weak, &local_ok };          /* (kf_kernel_t's parameters) */
+    HIPCHK(hipLaunchKernel((const void *)kf_kernel(ud), dim3(ug_kf_grid(C, n)), dim3(KF_NT), args, 0, st));
     return S3A_OK;
 }
 
-static int32_t
-kf_launch_c(s3a_uttdec_t *ud, int32_t n, const KfJob &J, int32_t C, hipStream_t st = NULL)
-{
-    if (ud->S.ne == 5) {
-        if (ud->S.pheurtype > 0) return ud->exact ? kf_launch_t<5, true, true>(ud, n, J, C, st) : kf_launch_t<5, false, true>(ud, n, J, C, st);
-        return ud->exact ? kf_launch_t<5, true>(ud, n, J, C, st) : kf_launch_t<5, false>(ud, n, J, C, st);
-    }
-    if (ud->S.pheurtype > 0) return ud->exact ? kf_launch_t<3, true, true>(ud, n, J, C, st) : kf_launch_t<3, false, true>(ud, n, J, C, st);
-    return ud->exact ? kf_launch_t<3, true>(ud, n, J, C, st) : kf_launch_t<3, false>(ud, n, J, C, st);
-}
-
-/* one launch, the cluster size the library's (KF_WINDOW blocks; a call without the relay) */
-static int32_t
-kf_launch(s3a_uttdec_t *ud, int32_t n, const KfJob &J)
-{
-    return kf_launch_c(ud, n, J, kf_choose_c(ud, n));
-}
-
-/* THE RELAY: a KF_QUEUE / KF_STATIC call as a chain of launches (KfJob.stop_at).  The first launch is what kf_launch would have made; when
+/* THE RELAY: a KF_QUEUE / KF_STATIC call as a chain of launches (KfJob.stop_at).  The first launch is the single launch's (ug_kf: c0); when
  * nothing is left to take and no more lanes are at work than fit the chip as clusters of 2 (then 4) workgroups, they hand themselves over
  * at their next frame boundary and the next launch -- enqueued here, up front, behind the first -- continues them that way.  A launch of
  * the chain that is handed nothing ends at once.  Only an engine that may size clusters for the whole device plans a chain (kf_alone; not
@@ -4562,20 +4349,9 @@ kf_launch_overlapped(s3a_uttdec_t *ud, int32_t n, KfJob J, const KfPlan &P)
 static int32_t
 kf_launch_chain(s3a_uttdec_t *ud, int32_t n, KfJob J, const KfPlan *ov = NULL)
 {
-    /* (kf_relay_at, the tests' switch: the chain from one workgroup per lane on, however few the lanes; scoring beside the search: one per lane) */
-    const int32_t C0 = (s3a_variants()->kf_relay_at > 0 && ud->kf_cluster_opt == 0) || ov ? 1 : kf_choose_c(ud, n), usable = kf_usable_per_xcd(ud), W = KF_ST_WORDS + ud->n_lanes;
-    int32_t st_c[KF_STAGES], st_cap[KF_STAGES], n_st = 0;
-    /* (kf_relay_at, the tests' switch: the chain whatever else runs on the device -- the caller answers for co-residency, as with .cluster) */
-    if (ud->d_kfrelay && ud->kf_cluster_opt == 0 && (kf_alone(ud) || s3a_variants()->kf_relay_at > 0) && !s3a_variants()->kf_no_relay) {
-        int32_t prev_n = n, prev_c = C0;
-        for (int32_t c = 2; c <= 4 && n_st < KF_STAGES; c *= 2) {
-            int32_t cap = 8 * (usable / c);
-            if (s3a_variants()->kf_relay_at > 0) cap = min(cap, max(1, s3a_variants()->kf_relay_at / (c / 2)));
-            if (c <= prev_c || (long long)cap * 5 > (long long)prev_n * 4) continue;      /* (fewer lanes than 0.8 of the launch before) */
-            st_c[n_st] = c; st_cap[n_st] = cap; n_st++;
-            prev_n = cap; prev_c = c;
-        }
-    }
+    ud->call.alone = kf_alone(ud);          /* (as of this launch: the clusters sized here spin on one another) */
+    const UgKf G = ug_kf(ud->shape, ud->geom, ud->call, n, ov != NULL);
+    const int32_t C0 = G.c0, n_st = G.n_st, st_c[KF_STAGES] = { G.st_c1, G.st_c2 }, st_cap[KF_STAGES] = { G.st_cap1, G.st_cap2 }, W = KF_ST_WORDS + ud->n_lanes;
     if (n_st == 0) return ov ? kf_launch_overlapped(ud, n, J, *ov) : kf_launch_c(ud, n, J, C0);
     HIPCHK(hipMemsetAsync(ud->d_kfrelay, 0, ((size_t)(KF_STAGES + 1) * W + (size_t)3 * ud->n_lanes) * 4, ud->stream));
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)ud->d_kfrelay, n, 1, ud->stream));           /* (the first launch's lanes at work) */
@@ -4603,7 +4379,7 @@ enqueue_block(s3a_uttdec_t *ud, int32_t n, int32_t fg0, int32_t nf)
     memset(&J, 0, sizeof J);
     J.mode = KF_WINDOW; J.fg0 = fg0; J.n_fr = nf;
     ud->kf_n_score++; ud->kf_n_frames++;            /* (s3a_uttdec_last_parts: a block is a scoring pass + a launch) */
-    return kf_launch(ud, n, J);
+    return kf_launch_c(ud, n, J, ug_kf_choose_c(ud->shape, ud->geom, kf_alone(ud), n));      /* (one launch, the cluster size the library's, alone or not as of now) */
 }
 
 /* a time mark on the engine's stream (pairs of them bracket the scoring launches and ku_frames: kf_collect) */
@@ -4726,12 +4502,10 @@ kf_static_group(s3a_uttdec_t *ud, int32_t m, const long long *row0, size_t g0, s
 }
 
 /* s3a_uttdec_decode through ku_frames: lane z decodes utterance z, all of its frames in one launch.  feat_dev[z]: the lane's
- * features on the device.  Returns S3A_EUNSUP when the scores do not fit (the caller then decodes in window blocks). */
+ * features on the device; P: the call's plan (KFP_ONE), whose rows fit the device (ug_route). */
 static int32_t
-kf_decode_static(s3a_uttdec_t *ud, int32_t n_utt, const int32_t *n_frames)
+kf_decode_static(s3a_uttdec_t *ud, int32_t n_utt, const KfPlan &P)
 {
-    const KfPlan P = kf_plan(n_utt, n_frames, KFP_ONE, 0, true, 0, 0, 0, false);
-    if (P.max_rows > sb_budget_rows(ud)) return S3A_EUNSUP;
     std::vector<const float *> fd((size_t)n_utt);
     for (int32_t z = 0; z < n_utt; z++) fd[z] = ud->h_ctx_up[z].feat;
     int32_t rc;
@@ -4750,23 +4524,15 @@ kf_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat_dev, c
     /* SCORING BESIDE THE SEARCH (kf_launch_overlapped): only a LEAD of the first n1 takes' utterances -- their first kf_overlap_lead frames --
      * is scored up front; the rest is scored by the companion shape in the halves of the CUs that n1 lanes leave free: first those utterances'
      * later frames in rounds of R groups each, with *f_ready saying how far all of them are scored, then the other utterances; the other lanes
-     * start when it is through.  (kf_overlap_whole: the first n1 utterances WHOLE up front, as before the rounds.)  Only where the plan's
-     * premise holds -- an engine that sizes its launches for the whole device (as the relay), two lanes per CU, more utterances than lanes --
-     * and only for the plain call: one part (the plan drops n1 otherwise), no second pass, no look-ahead heuristic, no kept lattices.
-     * s3a_variants_t: kf_overlap = 1 asks for it (KF_OVERLAP_DEFAULT: without being asked), kf_overlap_n1 > 0 forces it with that many first
-     * lanes (the tests' small engines; the caller answers for co-residency), kf_no_overlap: never. */
+     * start when it is through.  (kf_overlap_whole: the first n1 utterances WHOLE up front, as before the rounds.)  Where it is done, with how
+     * many first lanes, and the lead and the rounds the plan is given: ug_kf / ug_kf_rounds (s3a_uttgeom.h); the plan drops n1 again when
+     * the queue goes through in more than one part. */
     const s3a_variants_t *va = s3a_variants();
-    int32_t n1 = 0;
-    if (!va->kf_no_overlap && !ud->dag && ud->S.pheurtype == 0 && !ud->q_keep_lat && n_utt > ud->n_lanes && ud->kf_cluster_opt == 0 && ud->d_kfleft) {
-        const int32_t n_cu = max(1, ud->g->dev->n_cu);
-        if (va->kf_overlap_n1 > 0) { if (va->kf_overlap_n1 < ud->n_lanes) n1 = va->kf_overlap_n1; }
-        else if ((KF_OVERLAP_DEFAULT || va->kf_overlap) && kf_alone(ud) && ud->n_lanes > n_cu && ud->n_lanes / 2 <= n_cu && kf_choose_c(ud, ud->n_lanes) == 1)
-            n1 = ud->n_lanes / 2;
-    }
-    const int32_t lead_g = (max(0, va->kf_overlap_lead) + UW_FB - 1) / UW_FB;
+    int32_t n1 = ug_kf(ud->shape, ud->geom, ud->call, ud->n_lanes, 0).n1;
     const auto plan = [&](int32_t first) {
-        return kf_plan(n_utt, n_frames, KFP_BUDGET, budget, va->kf_queue_in_order != 0, first, lead_g > 0 ? lead_g : KF_OVERLAP_LEAD / UW_FB,
-                       va->kf_overlap_round > 0 ? va->kf_overlap_round : max(1, SB_PIECE / max(1, first)), va->kf_overlap_whole != 0);
+        int32_t lead_g, round_g;
+        ug_kf_rounds(ud->call, first, &lead_g, &round_g);
+        return kf_plan(n_utt, n_frames, KFP_BUDGET, budget, va->kf_queue_in_order != 0, first, lead_g, round_g, va->kf_overlap_whole != 0);
     };
     KfPlan K = plan(n1);
     if (K.max_rows > budget) { s3a_set_error("s3a_uttdec_decode_queue: an utterance's scores (%zu rows) do not fit the device", K.max_rows); return S3A_ENOMEM; }
@@ -4847,7 +4613,7 @@ graph_for(s3a_uttdec_t *ud, int32_t n, hipGraphExec_t *out)
     hipGraphExec_t exec = NULL;
     if (hipStreamBeginCapture(ud->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { s3a_set_error("s3a_uttdec: hipStreamBeginCapture failed: %s", hipGetErrorString(hipGetLastError())); return S3A_EHIP; }
     int32_t rc = S3A_OK;
-    for (int32_t j = 0; j < G && rc == S3A_OK; j++) rc = enqueue_frame(ud, n, j, false);
+    for (int32_t j = 0; j < G && rc == S3A_OK; j++) rc = enqueue_frame(ud, frame_geom(ud, n).fr, j, false);
     if (rc == S3A_OK) hipLaunchKernelGGL(ku_advance, dim3(1), dim3(64), 0, ud->stream, ud->d_fgbase, G);
     if (hipStreamEndCapture(ud->stream, &graph) != hipSuccess || !graph) { s3a_set_error("s3a_uttdec: hipStreamEndCapture failed: %s", hipGetErrorString(hipGetLastError())); return S3A_EHIP; }
     if (rc != S3A_OK) { (void)hipGraphDestroy(graph); return rc; }
@@ -4973,6 +4739,7 @@ uttdec_decode(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, const i
         return S3A_EINVAL;
     }
     HIPCHK(hipSetDevice(ud->device));
+    call_facts(ud, false, n_utt);
     int32_t rc, maxT = 0;
     ud->q_n = 0;
     ud->kf_n_score = ud->kf_n_frames = ud->kf_last_c = ud->kf_n_relay = ud->kf_overlapped = 0;         /* (s3a_uttdec_last_parts: all zero unless THIS call goes through ku_frames) */
@@ -4997,7 +4764,14 @@ uttdec_decode(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, const i
     rc = S3A_OK;
     tm[1] = now();
     if (hipEventRecord(ud->ev0, ud->stream) != hipSuccess) rc = S3A_EHIP;
-    if (ud->use_graph && ud->prof_every == 0) {
+    /* what the call runs as (ug_route): with every frame scored first when the plan's rows fit the device */
+    KfPlan P;
+    int32_t route = ug_route(ud->shape, ud->geom, ud->call, 0, 0);
+    if (route == UG_ROUTE_KF_STATIC) {
+        P = kf_plan(n_utt, n_frames, KFP_ONE, 0, true, 0, 0, 0, false);
+        route = ug_route(ud->shape, ud->geom, ud->call, (int64_t)P.max_rows, (int64_t)sb_budget_rows(ud));
+    }
+    if (route == UG_ROUTE_GRAPH) {
         hipGraphExec_t ge = NULL;
         const int32_t G = graph_block_frames(ud);
         rc = graph_for(ud, n_utt, &ge);
@@ -5006,18 +4780,15 @@ uttdec_decode(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, const i
             if (hipGraphLaunch(ge, ud->stream) != hipSuccess) { s3a_set_error("s3a_uttdec_decode: hipGraphLaunch failed: %s", hipGetErrorString(hipGetLastError())); rc = S3A_EHIP; }
         if (rc == S3A_OK && hipMemsetAsync(ud->d_fgbase, 0, 4, ud->stream) != hipSuccess) rc = S3A_EHIP;
     }
-    else if (kf_served(ud, n_utt)) {
-        /* every frame scored first, then each lane's utterance as one launch; in window blocks when the scores do not fit */
-        rc = kf_decode_static(ud, n_utt, n_frames);
-        if (rc == S3A_EUNSUP) {
-            rc = S3A_OK;
-            for (int32_t f = 0; f < maxT && rc == S3A_OK; f += ud->S.win_K)
-                rc = enqueue_block(ud, n_utt, f, min(ud->S.win_K, maxT - f));
-        }
+    else if (route == UG_ROUTE_KF_STATIC) { if (rc == S3A_OK) rc = kf_decode_static(ud, n_utt, P); }
+    else if (route == UG_ROUTE_WINDOW)
+        for (int32_t f = 0; f < maxT && rc == S3A_OK; f += ud->S.win_K)
+            rc = enqueue_block(ud, n_utt, f, min(ud->S.win_K, maxT - f));
+    else {
+        const UgFrame &G = frame_geom(ud, n_utt).fr;
+        for (int32_t f = 0; f < maxT && rc == S3A_OK; f++)
+            rc = enqueue_frame(ud, G, f, ud->prof_every > 0 && f % ud->prof_every == 0);
     }
-    else
-    for (int32_t f = 0; f < maxT && rc == S3A_OK; f++)
-        rc = enqueue_frame(ud, n_utt, f, ud->prof_every > 0 && f % ud->prof_every == 0);
     if (rc == S3A_OK && hipEventRecord(ud->ev1, ud->stream) != hipSuccess) rc = S3A_EHIP;
     /* (the second pass -- vithist_utt_end + lattice + best path for every lane -- follows the first pass's hypotheses below) */
     tm[2] = now();
@@ -5148,6 +4919,49 @@ s3a_kf_queue_plan(int32_t n_utt, const int32_t *n_frames, int32_t rule, int64_t 
     return S3A_OK;
 }
 
+/* the launch geometry (s3a_uttgeom.h) through the C ABI: records as int32_t arrays in the order s3a_utt_geometry_fields names */
+extern "C" const char *
+s3a_utt_geometry_fields(int32_t record)
+{
+    return ug_field_names(record);
+}
+
+/* ... the pure functions: host arithmetic, no device */
+extern "C" int32_t
+s3a_utt_geometry(const int32_t *shape, const int32_t *call, int32_t n, int32_t ov, int32_t score_slots, int64_t max_rows, int64_t budget,
+                 int32_t *engine, int32_t *frame, int32_t *window, int32_t *score, int32_t *companion, int32_t *kf, int32_t *route)
+{
+    if (!shape || !call || !engine || !frame || !window || !score || !companion || !kf || !route || n <= 0 || score_slots <= 0) return S3A_EINVAL;
+    UgShape s;
+    UgCall c;
+    memcpy(&s, shape, sizeof s); memcpy(&c, call, sizeof c);
+    if (s.n_lanes <= 0 || n > s.n_lanes || s.T <= 0 || s.N < 0 || s.maxn < 0 || s.CP <= 0 || s.Gpad < 0 || s.n_sen < s.n_ci_sen || s.n_ci_sen < 0) return S3A_EINVAL;
+    const UgEngine e = ug_engine(s);
+    const UgFrame f = ug_frame(s, e, n, c.hist_sort_launch);
+    const UgScore w = ug_score(s, ug_window_slots(e, n)), q = ug_score(s, score_slots), qc = ug_companion(s, score_slots);
+    const UgKf k = ug_kf(s, e, c, n, ov);
+    memcpy(engine, &e, sizeof e); memcpy(frame, &f, sizeof f); memcpy(window, &w, sizeof w); memcpy(score, &q, sizeof q);
+    memcpy(companion, &qc, sizeof qc); memcpy(kf, &k, sizeof k);
+    *route = ug_route(s, e, c, max_rows, budget);
+    return S3A_OK;
+}
+
+/* diagnostics: the shape a live engine was built from (with what came later: -pheurtype, ku_frames' occupancy and LDS once a call asked),
+ * the facts of its last call, and the records it holds and launches from for n lanes */
+extern "C" int32_t
+s3a_uttdec_geometry(const s3a_uttdec_t *ud, int32_t n, int32_t *shape, int32_t *call, int32_t *engine, int32_t *frame, int32_t *window, int32_t *kf)
+{
+    if (!ud || n <= 0 || n > ud->n_lanes || !shape || !call || !engine || !frame || !window || !kf) return S3A_EINVAL;
+    /* (computed here, as frame_geom does, not taken from or added to the engine's cache: nothing of the engine is written) */
+    s3a_uttdec_s::FrameGeom g;
+    g.fr = ug_frame(ud->shape, ud->geom, n, ud->call.hist_sort_launch);
+    g.win = ug_score(ud->shape, ug_window_slots(ud->geom, n));
+    const UgKf k = ug_kf(ud->shape, ud->geom, ud->call, n, ud->kf_overlapped);
+    memcpy(shape, &ud->shape, sizeof ud->shape); memcpy(call, &ud->call, sizeof ud->call); memcpy(engine, &ud->geom, sizeof ud->geom);
+    memcpy(frame, &g.fr, sizeof g.fr); memcpy(window, &g.win, sizeof g.win); memcpy(kf, &k, sizeof k);
+    return S3A_OK;
+}
+
 /* s3a_uttdec_queue_keep_lattices: the lanes `lanes[0 .. n)` have just gone through the second pass for the utterances utts[]: wait for the
  * stream and read their lattices back, before the lanes' tables are reused (the price of lattices out of a queue: the host waits once per
  * group / refill event) */
@@ -5196,16 +5010,17 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
     HIPCHK(hipSetDevice(ud->device));
     ud->kf_n_score = ud->kf_n_frames = ud->kf_last_c = ud->kf_n_relay = ud->kf_overlapped = 0;
     const UShared &S = ud->S;
-    const bool graph_mode = ud->use_graph && ud->prof_every == 0;
-    /* ku_frames (KF_QUEUE): the lanes take the utterances themselves -- no schedule, no refill events, no window boundaries */
-    const bool kfq = !graph_mode && kf_served(ud, min(ud->n_lanes, n_utt)) && !ud->dag && S.pheurtype == 0;
+    call_facts(ud, true, n_utt);
+    /* what the call runs as (ug_route).  ku_frames (KF_QUEUE): the lanes take the utterances themselves -- no schedule, no refill events,
+     * no window boundaries */
     /* ... and with the second pass (round 6): the queue as GROUPS of at most n_lanes utterances, longest first -- a group is lane z = its
      * z-th utterance from the first frame to the last in ONE ku_frames launch (KF_STATIC, with the relay), then every lane's hypothesis,
      * vithist_utt_end + the second pass while the tables are still the utterances' own, and lextree_utt_end; everything enqueued, nothing
      * waited for between groups (utterances of like length share a group, so a group's lanes end together).  Before: the frame as launches
      * with refill events, or -- asked for -- window blocks, the regime that lost to the launches. */
     /* (-pheurtype goes the same way: the look-ahead's tables are a LANE's -- made when the lane begins its utterance, ku_ci_ahead / ku_phn_heur) */
-    bool kfd = !graph_mode && kf_served(ud, min(ud->n_lanes, n_utt)) && (ud->dag != NULL || S.pheurtype > 0);
+    int32_t route = ug_route(ud->shape, ud->geom, ud->call, 0, 0);
+    const bool graph_mode = route == UG_ROUTE_GRAPH;
     /* utterances begin at window boundaries (the look-ahead pass scores K frames of all lanes); in graph mode at the blocks' */
     const int32_t n = min(ud->n_lanes, n_utt), E = graph_mode ? graph_block_frames(ud) : (S.win_K > 0 ? S.win_K : 1), D4x4 = S.D4 * 4, T = S.T;
     int32_t rc;
@@ -5218,11 +5033,12 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
         if (!feat[u]) { s3a_set_error("s3a_uttdec_decode_queue: utterance %d has no features", u); return S3A_EINVAL; }
         row0[u + 1] = row0[u] + (size_t)n_frames[u];
     }
-    KfPlan K;                       /* (kfd: the groups are the plan's parts) */
-    if (kfd) {
+    KfPlan K;                       /* (kfd: the groups are the plan's parts; a group's scores that do not fit: the launches) */
+    if (route == UG_ROUTE_KF_GROUPS) {
         K = kf_plan(n_utt, n_frames, KFP_LANES, (size_t)ud->n_lanes, false, 0, 0, 0, false);
-        if (K.max_rows > sb_budget_rows(ud)) kfd = false;           /* (a group's scores do not fit: the launches) */
+        route = ug_route(ud->shape, ud->geom, ud->call, (int64_t)K.max_rows, (int64_t)sb_budget_rows(ud));
     }
+    const bool kfq = route == UG_ROUTE_KF_QUEUE, kfd = route == UG_ROUTE_KF_GROUPS;
     /* features: one buffer, rows padded to the scorer's float4 stride, one copy */
     std::vector<const float *> fd((size_t)n_utt);
     if (!feat_on_device) {
@@ -5363,15 +5179,17 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
             if (rc == S3A_OK && hipGraphLaunch(ge, ud->stream) != hipSuccess) { s3a_set_error("s3a_uttdec_decode_queue: hipGraphLaunch failed: %s", hipGetErrorString(hipGetLastError())); rc = S3A_EHIP; }
         }
     }
-    else if (kf_served(ud, n) && ud->persist > 1)           /* (a queue with the second pass: ku_frames only when asked for -- window blocks keep all lanes in step) */
+    else if (route == UG_ROUTE_WINDOW)          /* (a queue with the second pass: ku_frames only when asked for -- window blocks keep all lanes in step) */
         for (int32_t fg = 0; fg < F_end && rc == S3A_OK; fg += E) {        /* (E = the window: refill events fall on its boundaries) */
             if (ei < evs.size() && evs[ei].f == fg) rc = run_event(evs[ei++]);
             if (rc == S3A_OK) rc = enqueue_block(ud, n, fg, min(E, F_end - fg));
         }
-    else
-    for (int32_t fg = 0; fg < F_end && rc == S3A_OK; fg++) {
-        if (ei < evs.size() && evs[ei].f == fg) rc = run_event(evs[ei++]);
-        if (rc == S3A_OK) rc = enqueue_frame(ud, n, fg, ud->prof_every > 0 && fg % ud->prof_every == 0);
+    else {
+        const UgFrame &G = frame_geom(ud, n).fr;
+        for (int32_t fg = 0; fg < F_end && rc == S3A_OK; fg++) {
+            if (ei < evs.size() && evs[ei].f == fg) rc = run_event(evs[ei++]);
+            if (rc == S3A_OK) rc = enqueue_frame(ud, G, fg, ud->prof_every > 0 && fg % ud->prof_every == 0);
+        }
     }
     while (rc == S3A_OK && ei < evs.size()) rc = run_event(evs[ei++]);
     if (graph_mode && rc == S3A_OK && hipMemsetAsync(ud->d_fgbase, 0, 4, ud->stream) != hipSuccess) rc = S3A_EHIP;

@@ -211,6 +211,9 @@ _SIGS = {
     "s3a_uttdec_decode_queue_dev": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     "s3a_queue_schedule": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "s3a_kf_queue_plan": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 7),
+    "s3a_utt_geometry_fields": (C.c_char_p, [C.c_int32]),
+    "s3a_utt_geometry": (C.c_int32, [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_int64] * 2 + [C.c_void_p] * 7),
+    "s3a_uttdec_geometry": (C.c_int32, [C.c_void_p, C.c_int32] + [C.c_void_p] * 6),
     "s3a_uttdec_queue_status": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "s3a_uttdec_queue_hyp": (C.c_int32, [C.c_void_p, C.c_int32, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     "s3a_uttdec_result": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
@@ -366,6 +369,48 @@ def kf_queue_plan(n_frames, rule, budget, in_order=False, n1=0, lead_groups=0, r
         raise S3AError(f"s3a_kf_queue_plan: error {rc}")
     out.update(zip(("max_rows", "n1", "g_first", "g_lead", "lead", "f_ready0"), (int(x) for x in sizes[3:])))
     return out
+
+
+GEOM_RECORDS = ("shape", "call", "engine", "frame", "score", "kf")      # s3a_utt_geometry_fields' record numbers
+GEOM_ROUTES = ("graph", "kf_static", "kf_queue", "kf_groups", "window", "frames")
+
+
+def geometry_fields(record):
+    """the int32 fields of a launch-geometry record (csrc/s3a_uttgeom.h), in order, as the library names them"""
+    return load().s3a_utt_geometry_fields(GEOM_RECORDS.index(record)).decode().rstrip(",").split(",")
+
+
+def _geom_in(record, d):
+    names = geometry_fields(record)
+    unknown = set(d) - set(names)
+    if unknown:
+        raise S3AError(f"launch geometry: no field {sorted(unknown)} in the {record} record")
+    return np.array([int(d.get(k, 0)) for k in names], np.int32)
+
+
+def _geom_out(record):
+    return np.zeros(len(geometry_fields(record)), np.int32)
+
+
+def _geom_dict(record, a):
+    return dict(zip(geometry_fields(record), (int(x) for x in a)))
+
+
+def utt_geometry(shape, call, n, ov=0, score_slots=8, max_rows=0, budget=0):
+    """the utterance engine's launch geometry as pure functions of a shape (csrc/s3a_uttgeom.h; host arithmetic, no device).  shape, call:
+    dicts of the records' fields (what they leave out is 0) -> dict of dicts: engine, frame and window (n lanes), score and companion
+    (score_slots slots), kf (n lanes; ov: scored beside the search), and route (a name of GEOM_ROUTES)"""
+    out = {k: _geom_out(r) for k, r in (("engine", "engine"), ("frame", "frame"), ("window", "score"), ("score", "score"),
+                                        ("companion", "score"), ("kf", "kf"))}
+    route = C.c_int32()
+    s, c = _geom_in("shape", shape), _geom_in("call", call)
+    rc = load().s3a_utt_geometry(_p(s), _p(c), int(n), int(ov), int(score_slots), int(max_rows),
+                                 int(budget), *[_p(a) for a in out.values()], C.byref(route))
+    if rc != S3A_OK:
+        raise S3AError(f"s3a_utt_geometry: error {rc}")
+    res = {k: _geom_dict("score" if k in ("window", "score", "companion") else k, a) for k, a in out.items()}
+    res["route"] = GEOM_ROUTES[route.value]
+    return res
 
 
 def device_count() -> int:
@@ -1448,9 +1493,9 @@ def dag_cfg(b, keep, bestpathlw=None, min_endfr=None, maxedge=None, maxlmop=None
 
 class Variants(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("scan_chained", "calls_by_copy", "batch_no_shared", "batch_no_multi",
-                                         "no_frame_sync_kernel", "score_nt", "score_fpc", "resolve_sweep", "hist_sort_launch", "ps_overlap", "ps_score_by_gaussian",
+                                         "no_frame_sync_kernel", "score_nt", "score_fpc", "hist_sort_launch", "ps_overlap", "ps_score_by_gaussian",
                                          "kf_queue_in_order", "kf_no_relay", "kf_relay_at",
-                                         "kf_no_overlap", "kf_overlap", "kf_overlap_n1", "uw_companion",
+                                         "kf_no_overlap", "kf_overlap_n1", "uw_companion",
                                          "kf_overlap_lead", "kf_overlap_round", "kf_overlap_whole", "kf_overlap_hold")]
 
 
@@ -1540,8 +1585,7 @@ class UttResult(C.Structure):
 
 class UttDecOpts(C.Structure):
     """s3a_uttdec_opts_t: the engine's tuning options (every variant gives the same bits)"""
-    _fields_ = [(k, C.c_int32) for k in ("many", "big_wl", "window", "window_fpc", "g_eval", "g_res", "scan_g", "gy", "sweep_k",
-                                         "no_multi", "framecheck", "times", "graph", "window_max", "scan_small_from", "persist", "cluster",
+    _fields_ = [(k, C.c_int32) for k in ("many", "big_wl", "window", "framecheck", "times", "graph", "scan_small_from", "persist", "cluster",
                                          "score_rows_max")] + [("reserved", C.c_int32 * 1)]
 
 
@@ -1658,6 +1702,14 @@ class UttDec:
         ns, nf, c = C.c_int32(), C.c_int32(), C.c_int32()
         check(self.L.s3a_uttdec_last_parts(self.h, C.byref(sm), C.byref(ns), C.byref(fm), C.byref(nf), C.byref(c)), self.L)
         return dict(score_ms=sm.value, n_score=ns.value, frames_ms=fm.value, n_frames=nf.value, cluster=c.value)
+
+    def geometry(self, n):
+        """-> dict of dicts: the shape this engine was built from, its last call's facts, and the launch-geometry records it holds for n
+        lanes: engine, frame, window, kf (s3a_uttdec_geometry; utt_geometry has the pure functions)"""
+        out = {k: _geom_out(r) for k, r in (("shape", "shape"), ("call", "call"), ("engine", "engine"), ("frame", "frame"),
+                                            ("window", "score"), ("kf", "kf"))}
+        check(self.L.s3a_uttdec_geometry(self.h, int(n), *[_p(a) for a in out.values()]), self.L)
+        return {k: _geom_dict("score" if k == "window" else k, a) for k, a in out.items()}
 
     def last_overlap(self):
         """-> dict(overlapped, resumed) of the last decode: the queue was scored beside the search (last_parts' two spans then overlap);

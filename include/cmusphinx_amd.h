@@ -754,19 +754,16 @@ s3a_uttdec_t *s3a_uttdec_init(const s3a_lexsearch_t *proto, s3a_mgau_model_t *g,
 /* The same with the engine's tuning options as arguments (all zero / -1 = the library's choice; every variant gives the
  * same bits): many = lanes from which the grids / kernels for many lanes per launch are used (default 32); big_wl = the word
  * level's candidate phases as launches of their own (-1: by the beams' width); window = frames per look-ahead scoring pass
- * (-1: 8, or up to window_max for ~1024 (lane, frame) slots per pass; 0: per-frame scoring kernels), window_fpc = slots per workgroup chunk of that pass;
- * g_eval / g_res / scan_g / gy / sweep_k = grid sizes of the HMM evaluation, the resolve kernels, the scan, the gated scorer and
- * the nodes per thread of the resolve sweep; no_multi = no shared CD pass of the per-frame scorer; framecheck = run the
+ * (-1: 8; 0: per-frame scoring kernels); framecheck = run the
  * per-frame invariant kernel; times = print the host-side phases of every decode to stderr; graph = HIP-graph replay of the
- * frames' launches (below).  s3a_uttdec_init is
+ * frames' launches (below).  Every grid size follows from these and the model's shape (csrc/s3a_uttgeom.h).  s3a_uttdec_init is
  * s3a_uttdec_init_opts with opts = NULL (defaults); the library never reads the environment for these:
  * s3a_uttdec_opts_from_env fills the struct from the S3A_UTT_* variables for hosts that want that (the drop-in program,
  * the test harness). */
 typedef struct {
-    int32_t many, big_wl, window, window_fpc, g_eval, g_res, scan_g, gy, sweep_k, no_multi, framecheck, times;
+    int32_t many, big_wl, window, framecheck, times;
     int32_t graph;          /* 1: the frames' launches are captured ONCE as a HIP graph (a block of `window` frames per lane count)
                              * and replayed block after block: one graph launch per block instead of ~13 kernel launches per frame */
-    int32_t window_max;     /* > 0: the longest look-ahead window the library may choose (lane refill happens at window boundaries) */
     int32_t scan_small_from; /* lanes per launch from which the scan uses 256-thread workgroups (0: 64) */
     int32_t persist;        /* the frames of a look-ahead window as ONE launch (ku_frames: a lane = a persistent 512-thread workgroup, or
                              * a cluster of them, that walks the frame's steps with barriers instead of launch boundaries -- the
@@ -831,6 +828,23 @@ int32_t s3a_queue_schedule(int32_t n_lanes, int32_t boundary, int32_t n_utt, con
 int32_t s3a_kf_queue_plan(int32_t n_utt, const int32_t *n_frames, int32_t rule, int64_t budget, int32_t in_order, int32_t n1,
                           int32_t lead_groups, int32_t round_groups, int32_t whole, int64_t *sizes, int32_t *order, int32_t *cut,
                           int64_t *row0, int64_t *g_at, int64_t *groups, int64_t *steps);
+/* the engine's launch geometry (csrc/s3a_uttgeom.h has the records, their fields and the rules), host arithmetic on the shape alone (no
+ * device).  A record is a struct of int32_t fields only: s3a_utt_geometry_fields(record) names them, comma separated, in order (record 0 =
+ * the shape, 1 = a call's facts, 2 = the engine's geometry, 3 = a frame's launches, 4 = a scoring pass, 5 = a ku_frames call), so that a
+ * host lays the records out by name from the library itself.  shape, call: in; n = lanes of the call, ov = its first ku_frames launch is
+ * the one scored beside the search, score_slots = (lane, frame) slots of an up-front scoring pass, max_rows / budget = the rows of senone
+ * scores the call's largest part needs / the device holds.  Out: the engine's record, the frame's for n lanes, the scoring passes of a
+ * look-ahead window of n lanes, of score_slots slots, and of score_slots slots in the shape that fits beside ku_frames, the ku_frames
+ * record, and *route = what the call runs as (0 graph blocks, 1 KF_STATIC, 2 KF_QUEUE, 3 the second-pass / -pheurtype queue as groups of
+ * static launches, 4 window blocks, 5 launches per frame). */
+const char *s3a_utt_geometry_fields(int32_t record);
+int32_t s3a_utt_geometry(const int32_t *shape, const int32_t *call, int32_t n, int32_t ov, int32_t score_slots, int64_t max_rows,
+                         int64_t budget, int32_t *engine, int32_t *frame, int32_t *window, int32_t *score, int32_t *companion,
+                         int32_t *kf, int32_t *route);
+/* diagnostics, read-only: the shape a live engine was built from, the facts of its last call, its geometry, and the records it launches
+ * from for n lanes (computed as the engine computes them, from what it holds; nothing of the engine is written) */
+int32_t s3a_uttdec_geometry(const s3a_uttdec_t *ud, int32_t n, int32_t *shape, int32_t *call, int32_t *engine, int32_t *frame, int32_t *window,
+                            int32_t *kf);
 /* diagnostics: time lane z's last utterance spent in each phase of the one-workgroup word level, in 100 MHz ticks
  * ([0] frame record + exits, [1] P1, [2] P2 trigram scores, [3] P3 hash insert, [4] P4 entry places, [5] P5 staging,
  * [6] pruning, [7] table + LM contexts, [8] word transitions) */
@@ -846,7 +860,7 @@ int32_t s3a_uttdec_wl_ticks(s3a_uttdec_t *ud, int32_t lane, long long *out16);
  * up-front scoring (ku_score_window: milliseconds, launches) and ku_frames itself; *cluster = workgroups per lane.  All zero when
  * the call ran the frame as separate launches (fewer lanes than pay for ku_frames, an option it does not serve, persist = -1). */
 int32_t s3a_uttdec_last_parts(s3a_uttdec_t *ud, double *score_ms, int32_t *n_score, double *frames_ms, int32_t *n_frames, int32_t *cluster);
-/* ... a queue that was scored BESIDE the search (s3a_variants_t.kf_overlap ...): *overlapped = 1, and then score_ms spans the first scoring
+/* ... a queue that was scored BESIDE the search (s3a_variants_t.kf_no_overlap ...): *overlapped = 1, and then score_ms spans the first scoring
  * launch's start to the last one's end, frames_ms the first ku_frames launch's start to the last one's end -- the two spans OVERLAP, their
  * sum is more than the call took.  *resumed: lanes that found their next utterance (or, s3a_uttdec_last_overlap2, their next frame) not scored
  * yet, left their launch and were taken up again by the launch behind the scoring. */
@@ -1278,7 +1292,6 @@ typedef struct {
     int32_t batch_no_shared, batch_no_multi;    /* s3a_batch: one scoring launch per decoder instead of the shared-model passes */
     int32_t no_frame_sync_kernel;   /* single-frame scoring through the general kernel */
     int32_t score_nt, score_fpc;    /* whole-utterance scoring: workgroup size (256 / 512 / 1024; 0 = 512), frames per chunk (0 = chosen) */
-    int32_t resolve_sweep;          /* whole-utterance engine, many lanes: find the nodes a parent may enter by the sweep over all nodes (round 2/3) instead of from the propagating HMMs' child lists */
     int32_t hist_sort_launch;       /* whole-utterance engine: the histogram sort as a launch of its own in every frame (default: on the count's launch, when a frame needs it) */
     int32_t ps_overlap;             /* s3a_psfwd_decode_queue: score the queue's later utterances BESIDE the search (second stream) instead of before it */
     int32_t ps_score_by_gaussian;   /* pocketsphinx batch scoring: the lane-per-Gaussian kernel (k_ps_cont_slots) instead of lane-per-frame */
@@ -1292,7 +1305,6 @@ typedef struct {
      * for the plain call of an engine alone on its device with two lanes per CU (one part, no second pass, no -pheurtype, no kept lattices,
      * more utterances than lanes); every other call is enqueued as before. */
     int32_t kf_no_overlap;          /* never (A/B) */
-    int32_t kf_overlap;             /* where the library does not do it by default: do it where the conditions hold */
     int32_t kf_overlap_n1;          /* > 0: do it whatever the engine's size and whatever else runs on the device, with that many first lanes (< lanes;
                                      * tests use it with a handful of lanes; the call's own conditions still hold) */
     int32_t uw_companion;           /* the up-front scoring passes of ku_frames' calls through the companion shape (256 threads, the LDS a CU has left
