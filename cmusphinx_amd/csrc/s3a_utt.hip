@@ -29,7 +29,6 @@
 #include <limits.h>
 #include <vector>
 #include <deque>
-#include <map>
 #include <atomic>
 #include <mutex>
 #include <algorithm>
@@ -48,6 +47,7 @@
 #include "s3a_hostmem.h"
 #include "s3a_kfplan.h"
 #include "s3a_uttgeom.h"
+#include "s3a_qsched.h"
 
 /* A pointer that came out of a structure in memory is a GENERIC pointer to the compiler; what it makes of an access through one is
  * flat_load / flat_store -- counted by the LDS counter as well as the memory counter, so that every wait for an LDS read waits for
@@ -3985,53 +3985,6 @@ utt_context(const s3a_uttdec_t *ud, UCtx &x, const float *d_feat, int32_t nfr, i
     return S3A_OK;
 }
 
-/* srch_TST_begin (srch_time_switch_tree.c:457-512) for one lane: the dummy <s> history entry, the
- * root entries with silence as left context into unigram tree 0 and filler tree n_lextree */
-static int32_t
-lane_begin(s3a_uttdec_t *ud, int32_t z, const float *feat, int32_t nfr, int32_t feat_stride, bool feat_on_device)
-{
-    HostLane &hl = ud->lane[z];
-    const int32_t D4x4 = ud->S.D4 * 4;
-    int32_t rc;
-    if (nfr <= 0 || nfr > ud->max_frames) { s3a_set_error("s3a_uttdec_decode: %d frames (1..%d)", nfr, ud->max_frames); return S3A_EINVAL; }
-    /* features, rows padded to the scorer's float4 stride */
-    const float *d_feat_use = feat;
-    if (!feat_on_device) {
-        const size_t need = (size_t)nfr * D4x4;
-        /* (buffers grow with slack: every hipMalloc / hipHostMalloc / free stalls ALL streams of the device, the other
-         * engines' too -- a lane must not pay that each time its utterance is a little longer than the last) */
-        const size_t grow = (size_t)min(ud->max_frames, max(nfr + nfr / 2, 1024)) * D4x4;
-        if (hl.feat_d.reserve(ud->mem, S3A_GROW_DEV, need, grow) != S3A_OK) { s3a_set_error("s3a_uttdec_decode: feature buffer"); return S3A_ENOMEM; }
-        if (hl.feat_h.reserve(ud->mem, S3A_GROW_PIN, need, grow) != S3A_OK) { s3a_set_error("s3a_uttdec_decode: pinned feature buffer"); return S3A_ENOMEM; }
-        for (int32_t t = 0; t < nfr; t++) {
-            float *row = hl.feat_h.h + (size_t)t * D4x4;
-            memcpy(row, feat + (size_t)t * feat_stride, sizeof(float) * ud->veclen);
-            for (int32_t k = ud->veclen; k < D4x4; k++) row[k] = 0.0f;
-        }
-        HIPCHK(hipMemcpyAsync(hl.feat_d.d, hl.feat_h.h, need * 4, hipMemcpyHostToDevice, ud->stream));
-        d_feat_use = hl.feat_d.d;
-    }
-    else if (feat_stride != D4x4) {
-        s3a_set_error("s3a_uttdec_decode_dev: device features must have rows of %d floats (zero padded)", D4x4);
-        return S3A_EINVAL;
-    }
-    hl.nfr = nfr;
-    /* lextree + scorer state as after lextree_utt_end / at srch_TST_begin */
-    if ((rc = lane_scrub(ud, z)) != S3A_OK) return rc;
-    /* (lextree_utt_end, srch_TST_begin's resets and the history table's entry 0: ku_lanes_end / ku_lanes_begin, all
-     * lanes in two launches -- uttdec_decode; here only the host-side bookkeeping of the lane's objects) */
-    hl.ls->cur = 0;
-    hl.ls->last_nnxt = 0; hl.ls->hist_bound = 0; hl.ls->row_bound = 1;
-    hl.ls->nnxt_t.assign(hl.ls->n_tree, 0);
-    hl.sc->skip_count = 0;
-    UCtx &x = *hl.h_ctx;
-    if (hl.epoch < 1) hl.epoch = 1;
-    if ((rc = utt_context(ud, x, d_feat_use, nfr, hl.epoch, 0, -1)) != S3A_OK) return rc;
-    hl.epoch += nfr + 1;
-    ud->h_ctx_up[z] = x;            /* (uploaded with the other lanes': uttdec_decode) */
-    return S3A_OK;
-}
-
 /* ---- the launch geometry as the engine holds it (s3a_uttgeom.h has the rules) ---- */
 static_assert(UGC_DBLOCK == DBLOCK && UGC_RSBLOCK == RSBLOCK && UGC_M3BLOCK == M3BLOCK && UGC_SCAN_THREADS == SCAN_THREADS && UGC_UR_K == UR_K
               && UGC_UW_FB == UW_FB && UGC_USEL_G == USEL_G && UGC_UG_FB == UG_FB && UGC_UG_MAX == UG_MAX && UGC_WL_THREADS == WL_THREADS
@@ -4730,6 +4683,104 @@ report_stopped(const char *who, int32_t utt, int32_t frame, int32_t e)
     return (e & (WL_E_EXITS | WL_E_CAND | WL_E_TABLE | WL_E_CALLS)) ? S3A_ENOMEM : S3A_EINVAL;
 }
 
+/* an utterance's features for the scorer: nfr rows of feat_stride floats into rows of the scorer's float4 stride, padding zero */
+static void
+stage_features(const s3a_uttdec_t *ud, float *dst, const float *feat, int32_t nfr, int32_t feat_stride)
+{
+    const int32_t D4x4 = ud->S.D4 * 4;
+    for (int32_t t = 0; t < nfr; t++) {
+        float *row = dst + (size_t)t * D4x4;
+        memcpy(row, feat + (size_t)t * feat_stride, sizeof(float) * ud->veclen);
+        for (int32_t k = ud->veclen; k < D4x4; k++) row[k] = 0.0f;
+    }
+}
+
+/* the host-side bookkeeping of a lane's objects as after lextree_utt_end / at srch_TST_begin (on the device: ku_lanes_end / ku_lanes_begin,
+ * all lanes in two launches); k_dec_scan's stamps begin at 1 */
+static void
+lane_host_reset(HostLane &hl)
+{
+    hl.ls->cur = 0;
+    hl.ls->last_nnxt = 0; hl.ls->hist_bound = 0; hl.ls->row_bound = 1;
+    hl.ls->nnxt_t.assign(hl.ls->n_tree, 0);
+    hl.sc->skip_count = 0;
+    if (hl.epoch < 1) hl.epoch = 1;
+}
+
+/* the engine's two timing events live as long as the engine (the per-launch events of profiled frames are destroyed on every way out) */
+static int32_t
+call_events(s3a_uttdec_t *ud, const char *who)
+{
+    if (!ud->ev0 && (hipEventCreate(&ud->ev0) != hipSuccess || hipEventCreate(&ud->ev1) != hipSuccess)) {
+        s3a_set_error("%s: hipEventCreate failed", who);
+        return S3A_EHIP;
+    }
+    return S3A_OK;
+}
+
+/* the engine frames [0, f_end) of n lanes on one of the launch routes: blocks replayed as a graph (whole blocks always -- the frames behind an
+ * utterance's end find nothing to do --, the device's frame counter zero before and after), window blocks (the last one as long as what is
+ * left) or the frame as launches.  event(f): what a boundary f has the host enqueue before its frames, f_end's included -- a queue's refill
+ * event (they fall on the graph's blocks and the windows' boundaries), nothing in a plain decode */
+template <class EV>
+static int32_t
+enqueue_steps(s3a_uttdec_t *ud, const char *who, int32_t route, int32_t n, int32_t f_end, EV event)
+{
+    const bool graph = route == UG_ROUTE_GRAPH, window = route == UG_ROUTE_WINDOW;
+    const int32_t step = graph ? graph_block_frames(ud) : window ? ud->S.win_K : 1;
+    hipGraphExec_t ge = NULL;
+    int32_t rc = graph ? graph_for(ud, n, &ge) : S3A_OK;
+    if (graph && rc == S3A_OK && hipMemsetAsync(ud->d_fgbase, 0, 4, ud->stream) != hipSuccess) rc = S3A_EHIP;
+    const UgFrame *G = graph || window ? NULL : &frame_geom(ud, n).fr;
+    for (int32_t f = 0; f < f_end && rc == S3A_OK; f += step) {
+        if ((rc = event(f)) != S3A_OK) break;
+        if (graph) {
+            if (hipGraphLaunch(ge, ud->stream) != hipSuccess) { s3a_set_error("%s: hipGraphLaunch failed: %s", who, hipGetErrorString(hipGetLastError())); rc = S3A_EHIP; }
+        }
+        else if (window) rc = enqueue_block(ud, n, f, min(step, f_end - f));
+        else rc = enqueue_frame(ud, *G, f, ud->prof_every > 0 && f % ud->prof_every == 0);
+    }
+    if (rc == S3A_OK) rc = event(f_end);
+    if (graph && rc == S3A_OK && hipMemsetAsync(ud->d_fgbase, 0, 4, ud->stream) != hipSuccess) rc = S3A_EHIP;
+    return rc;
+}
+
+/* srch_TST_begin (srch_time_switch_tree.c:457-512) for one lane: the dummy <s> history entry, the
+ * root entries with silence as left context into unigram tree 0 and filler tree n_lextree */
+static int32_t
+lane_begin(s3a_uttdec_t *ud, int32_t z, const float *feat, int32_t nfr, int32_t feat_stride, bool feat_on_device)
+{
+    HostLane &hl = ud->lane[z];
+    const int32_t D4x4 = ud->S.D4 * 4;
+    int32_t rc;
+    if (nfr <= 0 || nfr > ud->max_frames) { s3a_set_error("s3a_uttdec_decode: %d frames (1..%d)", nfr, ud->max_frames); return S3A_EINVAL; }
+    const float *d_feat_use = feat;
+    if (!feat_on_device) {
+        const size_t need = (size_t)nfr * D4x4;
+        /* (buffers grow with slack: every hipMalloc / hipHostMalloc / free stalls ALL streams of the device, the other
+         * engines' too -- a lane must not pay that each time its utterance is a little longer than the last) */
+        const size_t grow = (size_t)min(ud->max_frames, max(nfr + nfr / 2, 1024)) * D4x4;
+        if (hl.feat_d.reserve(ud->mem, S3A_GROW_DEV, need, grow) != S3A_OK) { s3a_set_error("s3a_uttdec_decode: feature buffer"); return S3A_ENOMEM; }
+        if (hl.feat_h.reserve(ud->mem, S3A_GROW_PIN, need, grow) != S3A_OK) { s3a_set_error("s3a_uttdec_decode: pinned feature buffer"); return S3A_ENOMEM; }
+        stage_features(ud, hl.feat_h.h, feat, nfr, feat_stride);
+        HIPCHK(hipMemcpyAsync(hl.feat_d.d, hl.feat_h.h, need * 4, hipMemcpyHostToDevice, ud->stream));
+        d_feat_use = hl.feat_d.d;
+    }
+    else if (feat_stride != D4x4) {
+        s3a_set_error("s3a_uttdec_decode_dev: device features must have rows of %d floats (zero padded)", D4x4);
+        return S3A_EINVAL;
+    }
+    hl.nfr = nfr;
+    /* lextree + scorer state as after lextree_utt_end / at srch_TST_begin */
+    if ((rc = lane_scrub(ud, z)) != S3A_OK) return rc;
+    lane_host_reset(hl);
+    UCtx &x = *hl.h_ctx;
+    if ((rc = utt_context(ud, x, d_feat_use, nfr, hl.epoch, 0, -1)) != S3A_OK) return rc;
+    hl.epoch += nfr + 1;
+    ud->h_ctx_up[z] = x;            /* (uploaded with the other lanes': uttdec_decode) */
+    return S3A_OK;
+}
+
 static int32_t
 uttdec_decode(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, const int32_t *n_frames,
               int32_t feat_stride, bool feat_on_device)
@@ -4755,13 +4806,7 @@ uttdec_decode(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, const i
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(ud->S.ctx_all, ud->h_ctx_up, sizeof(UCtx) * n_utt, hipMemcpyHostToDevice, ud->stream));
     if ((rc = enqueue_pheur_tables(ud, maxT, n_utt, NULL)) != S3A_OK) return rc;
-    /* (the engine's two timing events live as long as the engine; the per-launch events of profiled frames are destroyed
-     * on every way out) */
-    if (!ud->ev0 && (hipEventCreate(&ud->ev0) != hipSuccess || hipEventCreate(&ud->ev1) != hipSuccess)) {
-        s3a_set_error("s3a_uttdec_decode: hipEventCreate failed");
-        return S3A_EHIP;
-    }
-    rc = S3A_OK;
+    if ((rc = call_events(ud, "s3a_uttdec_decode")) != S3A_OK) return rc;
     tm[1] = now();
     if (hipEventRecord(ud->ev0, ud->stream) != hipSuccess) rc = S3A_EHIP;
     /* what the call runs as (ug_route): with every frame scored first when the plan's rows fit the device */
@@ -4771,24 +4816,8 @@ uttdec_decode(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, const i
         P = kf_plan(n_utt, n_frames, KFP_ONE, 0, true, 0, 0, 0, false);
         route = ug_route(ud->shape, ud->geom, ud->call, (int64_t)P.max_rows, (int64_t)sb_budget_rows(ud));
     }
-    if (route == UG_ROUTE_GRAPH) {
-        hipGraphExec_t ge = NULL;
-        const int32_t G = graph_block_frames(ud);
-        rc = graph_for(ud, n_utt, &ge);
-        if (rc == S3A_OK && hipMemsetAsync(ud->d_fgbase, 0, 4, ud->stream) != hipSuccess) rc = S3A_EHIP;
-        for (int32_t f = 0; f < maxT && rc == S3A_OK; f += G)
-            if (hipGraphLaunch(ge, ud->stream) != hipSuccess) { s3a_set_error("s3a_uttdec_decode: hipGraphLaunch failed: %s", hipGetErrorString(hipGetLastError())); rc = S3A_EHIP; }
-        if (rc == S3A_OK && hipMemsetAsync(ud->d_fgbase, 0, 4, ud->stream) != hipSuccess) rc = S3A_EHIP;
-    }
-    else if (route == UG_ROUTE_KF_STATIC) { if (rc == S3A_OK) rc = kf_decode_static(ud, n_utt, P); }
-    else if (route == UG_ROUTE_WINDOW)
-        for (int32_t f = 0; f < maxT && rc == S3A_OK; f += ud->S.win_K)
-            rc = enqueue_block(ud, n_utt, f, min(ud->S.win_K, maxT - f));
-    else {
-        const UgFrame &G = frame_geom(ud, n_utt).fr;
-        for (int32_t f = 0; f < maxT && rc == S3A_OK; f++)
-            rc = enqueue_frame(ud, G, f, ud->prof_every > 0 && f % ud->prof_every == 0);
-    }
+    if (rc == S3A_OK && route == UG_ROUTE_KF_STATIC) rc = kf_decode_static(ud, n_utt, P);
+    else if (rc == S3A_OK) rc = enqueue_steps(ud, "s3a_uttdec_decode", route, n_utt, maxT, [](int32_t) { return (int32_t)S3A_OK; });
     if (rc == S3A_OK && hipEventRecord(ud->ev1, ud->stream) != hipSuccess) rc = S3A_EHIP;
     /* (the second pass -- vithist_utt_end + lattice + best path for every lane -- follows the first pass's hypotheses below) */
     tm[2] = now();
@@ -4876,26 +4905,33 @@ s3a_uttdec_decode_dev(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat_
 extern "C" int32_t
 s3a_queue_schedule(int32_t n_lanes, int32_t boundary, int32_t n_utt, const int32_t *n_frames, int32_t *lane, int32_t *f0)
 {
-    if (n_lanes <= 0 || boundary <= 0 || n_utt <= 0 || !n_frames || !lane || !f0) return S3A_EINVAL;
-    const int32_t n = min(n_lanes, n_utt);
-    std::vector<int32_t> busy_until((size_t)n, 0);
-    std::vector<char> busy((size_t)n, 0);
-    int32_t next = 0;
+    if (!lane || !f0) return S3A_EINVAL;
+    const QSched Q = q_sched_refill(n_lanes, boundary, n_utt, n_frames, NULL);
+    if (Q.f_end < 0) return S3A_EINVAL;
+    std::copy(Q.lane.begin(), Q.lane.end(), lane); std::copy(Q.f0.begin(), Q.f0.end(), f0);
+    return Q.f_end;
+}
+
+/* the whole schedule of a queue call (s3a_qsched.h) as flat arrays: host arithmetic, no device.  groups: the form for groups of static launches,
+ * from the plan the engine makes for it */
+extern "C" int32_t
+s3a_queue_events(int32_t groups, int32_t n_lanes, int32_t boundary, int32_t n_utt, const int32_t *n_frames, const int32_t *epoch0, int32_t *sizes,
+                 int32_t *lane, int32_t *f0, int32_t *epoch, int32_t *last_utt, int32_t *epoch_after, int32_t *nfr_after, int32_t *events, int32_t *lists)
+{
+    if (n_lanes <= 0 || n_utt <= 0 || !n_frames || !sizes) return S3A_EINVAL;
     for (int32_t u = 0; u < n_utt; u++) if (n_frames[u] <= 0) return S3A_EINVAL;
-    for (long long F = 0;; F += boundary) {
-        if (F > INT_MAX - boundary) return S3A_EINVAL;
-        bool any = false;
-        for (int32_t z = 0; z < n; z++) {
-            if (busy[z] && busy_until[z] <= F) busy[z] = 0;
-            if (!busy[z] && next < n_utt) {
-                lane[next] = z; f0[next] = (int32_t)F;
-                busy_until[z] = (int32_t)F + n_frames[next]; busy[z] = 1;
-                next++;
-            }
-            any = any || busy[z];
-        }
-        if (!any) return (int32_t)F;
-    }
+    const QSched Q = groups ? q_sched_groups(kf_plan(n_utt, n_frames, KFP_LANES, (size_t)n_lanes, false, 0, 0, 0, false), n_frames, n_lanes)
+                            : q_sched_refill(n_lanes, boundary, n_utt, n_frames, epoch0);
+    if (Q.f_end < 0) return S3A_EINVAL;
+    const int32_t sz[4] = { (int32_t)Q.last_utt.size(), (int32_t)Q.events.size(), (int32_t)Q.lists.size(), Q.f_end };
+    std::copy(sz, sz + 4, sizes);
+    if (!lane) return S3A_OK;
+    if (!f0 || !epoch || !last_utt || !epoch_after || !nfr_after || !events || !lists) return S3A_EINVAL;
+    std::copy(Q.lane.begin(), Q.lane.end(), lane); std::copy(Q.f0.begin(), Q.f0.end(), f0); std::copy(Q.epoch.begin(), Q.epoch.end(), epoch);
+    std::copy(Q.last_utt.begin(), Q.last_utt.end(), last_utt); std::copy(Q.epoch_after.begin(), Q.epoch_after.end(), epoch_after);
+    std::copy(Q.nfr_after.begin(), Q.nfr_after.end(), nfr_after); std::copy(Q.lists.begin(), Q.lists.end(), lists);
+    for (const QEvent &e : Q.events) { *events++ = e.f; *events++ = e.o_end; *events++ = e.o_beg; *events++ = e.n_end; *events++ = e.n_beg; *events++ = e.max_nfr; }
+    return S3A_OK;
 }
 
 /* the plan of a ku_frames call (s3a_kfplan.h) as flat arrays: host arithmetic, no device */
@@ -5044,11 +5080,7 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
     if (!feat_on_device) {
         if ((rc = q_reserve(ud, ud->q_feat, S3A_GROW_DEV | S3A_GROW_PIN, row0[n_utt] * D4x4, "features")) != S3A_OK) return rc;
         for (int32_t u = 0; u < n_utt; u++) {
-            for (int32_t t = 0; t < n_frames[u]; t++) {
-                float *row = ud->q_feat.h + (row0[u] + t) * D4x4;
-                memcpy(row, feat[u] + (size_t)t * feat_stride, sizeof(float) * ud->veclen);
-                for (int32_t k = ud->veclen; k < D4x4; k++) row[k] = 0.0f;
-            }
+            stage_features(ud, ud->q_feat.h + row0[u] * D4x4, feat[u], n_frames[u], feat_stride);
             fd[u] = ud->q_feat.d + row0[u] * D4x4;
         }
         HIPCHK(hipMemcpyAsync(ud->q_feat.d, ud->q_feat.h, row0[n_utt] * D4x4 * 4, hipMemcpyHostToDevice, ud->stream));
@@ -5057,62 +5089,27 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
         if (feat_stride != D4x4) { s3a_set_error("s3a_uttdec_decode_queue_dev: device features must have rows of %d floats (zero padded)", D4x4); return S3A_EINVAL; }
         for (int32_t u = 0; u < n_utt; u++) fd[u] = feat[u];
     }
+    std::vector<int32_t> epoch0((size_t)n);
     for (int32_t z = 0; z < n; z++) {
         if ((rc = lane_scrub(ud, z)) != S3A_OK) return rc;
+        lane_host_reset(ud->lane[z]);
+        epoch0[z] = ud->lane[z].epoch;
+    }
+    /* the schedule (s3a_qsched.h: host arithmetic on the lengths): who runs where from when, who ends and who begins at which boundary */
+    const QSched Q = kfq ? QSched(n_utt, n) : kfd ? q_sched_groups(K, n_frames, n) : q_sched_refill(n, E, n_utt, n_frames, epoch0.data());
+    if (Q.f_end < 0) return S3A_EINVAL;
+    for (int32_t z = 0; z < n; z++) {
         HostLane &hl = ud->lane[z];
-        hl.ls->cur = 0; hl.ls->last_nnxt = 0; hl.ls->hist_bound = 0; hl.ls->row_bound = 1;
-        hl.ls->nnxt_t.assign(hl.ls->n_tree, 0);
-        hl.sc->skip_count = 0;
-        if (hl.epoch < 1) hl.epoch = 1;
+        hl.epoch = max(hl.epoch, Q.epoch_after[z]);         /* (the stamps never go back) */
+        hl.nfr = Q.nfr_after[z];
     }
-    /* the schedule (s3a_queue_schedule: host arithmetic on the lengths), then who ends and who begins at which boundary */
-    struct Ev { int32_t f, o_el, o_bl, n_end, n_beg, max_nfr; };
-    std::vector<Ev> evs;
-    std::vector<int32_t> sched, u_lane((size_t)n_utt), u_f0((size_t)n_utt), last_utt((size_t)n, -1);
     if ((rc = q_reserve(ud, ud->q_ctx, S3A_GROW_DEV | S3A_GROW_PIN, (size_t)n_utt, "contexts")) != S3A_OK) return rc;
-    if (kfq || kfd) {
-        for (int32_t u = 0; u < n_utt; u++)
-            if ((rc = utt_context(ud, ud->q_ctx.h[u], fd[u], n_frames[u], 1, 0, u)) != S3A_OK) return rc;
-        for (int32_t z = 0; z < n; z++) ud->lane[z].nfr = 0;
-        if (kfd) {              /* the groups' lane / utterance lists: [lanes 0 .. m - 1][their utterances] per group */
-            for (size_t p = 0; p + 1 < K.cut.size(); p++) {
-                const int32_t k0 = K.cut[p], m = K.cut[p + 1] - k0;
-                for (int32_t z = 0; z < m; z++) sched.push_back(z);
-                for (int32_t z = 0; z < m; z++) { sched.push_back(K.order[k0 + z]); last_utt[z] = K.order[k0 + z]; }
-            }
-        }
-    }
-    else {
-        const int32_t fe = s3a_queue_schedule(n, E, n_utt, n_frames, u_lane.data(), u_f0.data());
-        if (fe < 0) return fe;
-        struct Lists { std::vector<int32_t> el, eu, bl, bu; int32_t mx = 0; };
-        std::map<int32_t, Lists> at;
-        for (int32_t u = 0; u < n_utt; u++) {           /* (queue order = the order of a lane's utterances) */
-            const int32_t z = u_lane[u], F = u_f0[u], Fe = ((F + n_frames[u] + E - 1) / E) * E;
-            HostLane &hl = ud->lane[z];
-            if ((rc = utt_context(ud, ud->q_ctx.h[u], fd[u], n_frames[u], hl.epoch, F, u)) != S3A_OK) return rc;
-            hl.epoch += n_frames[u] + 1;
-            hl.nfr = n_frames[u];
-            last_utt[z] = u;
-            Lists &b = at[F];
-            b.bl.push_back(z); b.bu.push_back(u); b.mx = max(b.mx, n_frames[u]);
-            Lists &e = at[Fe];
-            e.el.push_back(z); e.eu.push_back(u);
-        }
-        for (auto &kv : at) {
-            const Lists &l = kv.second;
-            Ev e = { kv.first, (int32_t)sched.size(), 0, (int32_t)l.el.size(), (int32_t)l.bl.size(), l.mx };
-            sched.insert(sched.end(), l.el.begin(), l.el.end()); sched.insert(sched.end(), l.eu.begin(), l.eu.end());
-            e.o_bl = (int32_t)sched.size();
-            sched.insert(sched.end(), l.bl.begin(), l.bl.end()); sched.insert(sched.end(), l.bu.begin(), l.bu.end());
-            evs.push_back(e);
-        }
-    }
-    const int32_t F_end = evs.empty() ? 0 : evs.back().f;           /* (the last event only ends lanes) */
-    if ((rc = q_reserve(ud, ud->q_sched, S3A_GROW_DEV | S3A_GROW_PIN, sched.size(), "schedule")) != S3A_OK) return rc;
-    if (!sched.empty()) {
-        memcpy(ud->q_sched.h, sched.data(), sched.size() * 4);
-        HIPCHK(hipMemcpyAsync(ud->q_sched.d, ud->q_sched.h, sched.size() * 4, hipMemcpyHostToDevice, ud->stream));
+    for (int32_t u = 0; u < n_utt; u++)
+        if ((rc = utt_context(ud, ud->q_ctx.h[u], fd[u], n_frames[u], Q.epoch[u], Q.f0[u], u)) != S3A_OK) return rc;
+    if ((rc = q_reserve(ud, ud->q_sched, S3A_GROW_DEV | S3A_GROW_PIN, Q.lists.size(), "schedule")) != S3A_OK) return rc;
+    if (!Q.lists.empty()) {
+        memcpy(ud->q_sched.h, Q.lists.data(), Q.lists.size() * 4);
+        HIPCHK(hipMemcpyAsync(ud->q_sched.d, ud->q_sched.h, Q.lists.size() * 4, hipMemcpyHostToDevice, ud->stream));
     }
     HIPCHK(hipMemcpyAsync(ud->q_ctx.d, ud->q_ctx.h, sizeof(UCtx) * n_utt, hipMemcpyHostToDevice, ud->stream));
     /* results: a header per utterance + the word counter; the words packed (an utterance's hypothesis has at most one word
@@ -5136,63 +5133,44 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
     /* whatever the engine's last decode left active (it ends its lanes at the NEXT decode's beginning) */
     hipLaunchKernelGGL(ku_lanes_end, dim3(8, 2 * T, n), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, (const int32_t *)NULL, 0);
     HIPCHK(hipGetLastError());
-    auto run_event = [&](const Ev &e) -> int32_t {
-        const int32_t *el = ud->q_sched.d + e.o_el, *eu = el + e.n_end, *bl = ud->q_sched.d + e.o_bl, *bu = bl + e.n_beg;
-        int32_t erc;
-        if (e.n_end > 0 && (erc = enqueue_utts_end(ud, e.n_end, el, eu, sched.data() + e.o_el, sched.data() + e.o_el + e.n_end, P, n_utt, wcount)) != S3A_OK) return erc;
-        if (e.n_beg > 0) {
-            hipLaunchKernelGGL(ku_lanes_begin, dim3(32, 1, e.n_beg), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, B, bl, bu, (const UCtx *)ud->q_ctx.d);
-            if ((erc = enqueue_pheur_tables(ud, e.max_nfr, e.n_beg, bl)) != S3A_OK) return erc;
-        }
-        HIPCHK(hipGetLastError());
-        return S3A_OK;
+    /* an event's two halves: the end of the utterances of its ending lanes, and srch_TST_begin + the staged contexts of the utterances its
+     * beginning lanes take (the lists on the device, and for the lattices that are kept the same on the host) */
+    auto ev_end = [&](const QEvent &e) -> int32_t {
+        const int32_t *el = ud->q_sched.d + e.o_end, *eh = Q.lists.data() + e.o_end;
+        return e.n_end > 0 ? enqueue_utts_end(ud, e.n_end, el, el + e.n_end, eh, eh + e.n_end, P, n_utt, wcount) : (int32_t)S3A_OK;
     };
-    if (!ud->ev0 && (hipEventCreate(&ud->ev0) != hipSuccess || hipEventCreate(&ud->ev1) != hipSuccess)) {
-        s3a_set_error("s3a_uttdec_decode_queue: hipEventCreate failed");
-        return S3A_EHIP;
-    }
-    rc = S3A_OK;
+    auto ev_begin = [&](const QEvent &e) -> int32_t {
+        const int32_t *bl = ud->q_sched.d + e.o_beg;
+        if (e.n_beg == 0) return S3A_OK;
+        hipLaunchKernelGGL(ku_lanes_begin, dim3(32, 1, e.n_beg), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, B, bl, bl + e.n_beg, (const UCtx *)ud->q_ctx.d);
+        HIPCHK(hipGetLastError());
+        return enqueue_pheur_tables(ud, e.max_nfr, e.n_beg, bl);
+    };
+    if ((rc = call_events(ud, "s3a_uttdec_decode_queue")) != S3A_OK) return rc;
     if (hipEventRecord(ud->ev0, ud->stream) != hipSuccess) rc = S3A_EHIP;
-    size_t ei = 0;
-    if (kfq) {
-        if (rc == S3A_OK) rc = kf_decode_queue(ud, n_utt, fd.data(), n_frames, B, P, wcount);
-    }
-    else if (kfd) {
+    if (rc == S3A_OK && kfq) rc = kf_decode_queue(ud, n_utt, fd.data(), n_frames, B, P, wcount);
+    else if (rc == S3A_OK && kfd) {
         /* every group's scoring groups and rows loaded up front (the pinned tables must not change under the copies in flight) */
-        if (rc == S3A_OK) rc = sb_load(ud, K, fd.data());
+        rc = sb_load(ud, K, fd.data());
         ud->kf_n_score = ud->kf_n_frames = 0;
-        for (size_t p = 0; p + 1 < K.cut.size() && rc == S3A_OK; p++) {
-            const int32_t k0 = K.cut[p], m = K.cut[p + 1] - k0;
-            const int32_t *bl = ud->q_sched.d + (size_t)2 * k0, *bu = bl + m;
-            hipLaunchKernelGGL(ku_lanes_begin, dim3(32, 1, m), dim3(256), 0, ud->stream, ud->d_lanes, ud->S, B, bl, bu, (const UCtx *)ud->q_ctx.d);
-            if ((rc = enqueue_pheur_tables(ud, n_frames[K.order[k0]], m, bl)) != S3A_OK) break;       /* (the group's longest utterance is its first) */
-            if ((rc = kf_static_group(ud, m, ud->sb_row0.d + k0, K.g_at[p], K.g_at[p + 1] - K.g_at[p])) != S3A_OK) break;
-            rc = enqueue_utts_end(ud, m, bl, bu, sched.data() + (size_t)2 * k0, sched.data() + (size_t)2 * k0 + m, P, n_utt, wcount);
+        for (size_t p = 0; p < Q.events.size() && rc == S3A_OK; p++) {          /* (an event per part of the plan: its lanes begin, run, end) */
+            const QEvent &e = Q.events[p];
+            if ((rc = ev_begin(e)) != S3A_OK) break;
+            if ((rc = kf_static_group(ud, e.n_beg, ud->sb_row0.d + K.cut[p], K.g_at[p], K.g_at[p + 1] - K.g_at[p])) != S3A_OK) break;
+            rc = ev_end(e);
         }
     }
-    else if (graph_mode) {
-        hipGraphExec_t ge = NULL;
-        rc = graph_for(ud, n, &ge);
-        if (rc == S3A_OK && hipMemsetAsync(ud->d_fgbase, 0, 4, ud->stream) != hipSuccess) rc = S3A_EHIP;
-        for (int32_t fg = 0; fg < F_end && rc == S3A_OK; fg += E) {        /* (E = the graph's block: refill events fall between blocks) */
-            if (ei < evs.size() && evs[ei].f == fg) rc = run_event(evs[ei++]);
-            if (rc == S3A_OK && hipGraphLaunch(ge, ud->stream) != hipSuccess) { s3a_set_error("s3a_uttdec_decode_queue: hipGraphLaunch failed: %s", hipGetErrorString(hipGetLastError())); rc = S3A_EHIP; }
-        }
+    else if (rc == S3A_OK) {
+        /* (refill events fall between the graph's blocks, on the windows' boundaries; a queue with the second pass goes through window blocks
+         * only when asked for: they keep all lanes in step) */
+        size_t ei = 0;
+        rc = enqueue_steps(ud, "s3a_uttdec_decode_queue", route, n, Q.f_end, [&](int32_t f) -> int32_t {
+            if (ei == Q.events.size() || Q.events[ei].f != f) return S3A_OK;
+            const QEvent &e = Q.events[ei++];
+            const int32_t erc = ev_end(e);
+            return erc != S3A_OK ? erc : ev_begin(e);
+        });
     }
-    else if (route == UG_ROUTE_WINDOW)          /* (a queue with the second pass: ku_frames only when asked for -- window blocks keep all lanes in step) */
-        for (int32_t fg = 0; fg < F_end && rc == S3A_OK; fg += E) {        /* (E = the window: refill events fall on its boundaries) */
-            if (ei < evs.size() && evs[ei].f == fg) rc = run_event(evs[ei++]);
-            if (rc == S3A_OK) rc = enqueue_block(ud, n, fg, min(E, F_end - fg));
-        }
-    else {
-        const UgFrame &G = frame_geom(ud, n).fr;
-        for (int32_t fg = 0; fg < F_end && rc == S3A_OK; fg++) {
-            if (ei < evs.size() && evs[ei].f == fg) rc = run_event(evs[ei++]);
-            if (rc == S3A_OK) rc = enqueue_frame(ud, G, fg, ud->prof_every > 0 && fg % ud->prof_every == 0);
-        }
-    }
-    while (rc == S3A_OK && ei < evs.size()) rc = run_event(evs[ei++]);
-    if (graph_mode && rc == S3A_OK && hipMemsetAsync(ud->d_fgbase, 0, 4, ud->stream) != hipSuccess) rc = S3A_EHIP;
     if (rc == S3A_OK && hipEventRecord(ud->ev1, ud->stream) != hipSuccess) rc = S3A_EHIP;
     if (rc == S3A_OK && hipMemcpyAsync(ud->q_hdr.h, ud->q_hdr.d, ((size_t)n_utt * UH_N + 1) * 4, hipMemcpyDeviceToHost, ud->stream) != hipSuccess) rc = S3A_EHIP;
     if (rc == S3A_OK && ud->dag && hipMemcpyAsync(ud->q_dio.h, ud->q_dio.d, ((size_t)n_utt * DG_IO_N + 1) * 4, hipMemcpyDeviceToHost, ud->stream) != hipSuccess) rc = S3A_EHIP;
@@ -5213,7 +5191,7 @@ uttdec_decode_queue(s3a_uttdec_t *ud, int32_t n_utt, const float *const *feat, c
     /* a lane whose LAST utterance stopped in mid-frame starts the next decode from scratch (the others of its utterances
      * that stopped were scrubbed on the device when the lane took its next one) */
     for (int32_t z = 0; z < n; z++)
-        if (last_utt[z] >= 0 && ud->q_hdr.h[(size_t)last_utt[z] * UH_N + UH_ERR]) ud->lane[z].dirty = 1;
+        if (Q.last_utt[z] >= 0 && ud->q_hdr.h[(size_t)Q.last_utt[z] * UH_N + UH_ERR]) ud->lane[z].dirty = 1;
     for (int32_t u = 0; u < n_utt; u++) {
         const int32_t *h = ud->q_hdr.h + (size_t)u * UH_N;
         if (h[UH_ERR]) return report_stopped("s3a_uttdec_decode_queue", u, h[UH_CF], h[UH_ERR]);

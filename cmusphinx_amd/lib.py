@@ -210,6 +210,7 @@ _SIGS = {
     "s3a_uttdec_decode_queue": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     "s3a_uttdec_decode_queue_dev": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     "s3a_queue_schedule": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3a_queue_events": (C.c_int32, [C.c_int32] * 4 + [C.c_void_p] * 11),
     "s3a_kf_queue_plan": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 7),
     "s3a_utt_geometry_fields": (C.c_char_p, [C.c_int32]),
     "s3a_utt_geometry": (C.c_int32, [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_int64] * 2 + [C.c_void_p] * 7),
@@ -350,6 +351,31 @@ def queue_schedule(n_lanes, boundary, n_frames):
     if total < 0:
         raise S3AError(f"s3a_queue_schedule: error {total}")
     return lane, f0, int(total)
+
+
+def queue_events(n_lanes, boundary, n_frames, epoch0=None, groups=False):
+    """the whole schedule of a queue call (csrc/s3a_qsched.h; host arithmetic) -> dict: per utterance lane, f0, epoch; per lane last_utt,
+    epoch_after, nfr_after; events [n, 6] (f, o_end, o_beg, n_end, n_beg, max_nfr) into lists; f_end.  groups: the form for groups of static
+    launches (boundary and epoch0 play no part)"""
+    nf = np.ascontiguousarray(n_frames, np.int32)
+    n = min(int(n_lanes), len(nf))
+    e0 = None if epoch0 is None else np.ascontiguousarray(epoch0, np.int32)
+    if e0 is not None and len(e0) < n:
+        raise S3AError(f"s3a_queue_events: {len(e0)} epochs for {n} lanes")
+    sizes = np.zeros(4, np.int32)
+    args = (int(bool(groups)), int(n_lanes), int(boundary), len(nf), _p(nf), _p(e0), _p(sizes))
+    rc = load().s3a_queue_events(*args, *[None] * 8)
+    if rc != S3A_OK:
+        raise S3AError(f"s3a_queue_events: error {rc}")
+    lanes, n_ev, n_l, f_end = (int(x) for x in sizes)
+    out = {k: np.zeros(len(nf), np.int32) for k in ("lane", "f0", "epoch")}
+    out.update({k: np.zeros(lanes, np.int32) for k in ("last_utt", "epoch_after", "nfr_after")})
+    out.update(events=np.zeros((n_ev, 6), np.int32), lists=np.zeros(n_l, np.int32))
+    rc = load().s3a_queue_events(*args, *[_p(a) for a in out.values()])
+    if rc != S3A_OK:
+        raise S3AError(f"s3a_queue_events: error {rc}")
+    out["f_end"] = f_end
+    return out
 
 
 def kf_queue_plan(n_frames, rule, budget, in_order=False, n1=0, lead_groups=0, round_groups=0, whole=False):

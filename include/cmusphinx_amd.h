@@ -818,6 +818,17 @@ int32_t s3a_uttdec_queue_status(s3a_uttdec_t *ud, int32_t utt, int32_t *err, int
  * window, s3a_uttdec_window; 1 without look-ahead scoring).  Returns the engine frames the whole queue takes. */
 int32_t s3a_queue_schedule(int32_t n_lanes, int32_t boundary, int32_t n_utt, const int32_t *n_frames,
                            int32_t *lane, int32_t *f0);
+/* ... and the whole schedule (csrc/s3a_qsched.h has the terms), host arithmetic too: per utterance lane[], f0[] and the scan epoch[] it starts
+ * under, lanes starting at max(epoch0[z], 1) (epoch0 = NULL: zeros); per lane the last_utt[] it decodes (-1: none), epoch_after[] and
+ * nfr_after[] = the frames of that utterance; the events the host enqueues between frames, in frame order, events[6 x events] (engine frame,
+ * offset of the ending lists, of the beginning lists, ending lanes, beginning lanes, the longest beginning utterance), into lists[]: at an
+ * event's offsets [lanes][their utterances], ends before begins.  groups != 0: the form of the second-pass / -pheurtype queue instead, groups of
+ * static launches over n_lanes lanes (longest first; an event per group whose lanes begin and end the same utterances; every epoch 1, every f0 0;
+ * boundary and epoch0 unused).  sizes[4] = lanes (min(n_lanes, n_utt)), events, entries of lists, the engine frames the queue takes.
+ * lane = NULL: the sizes only; else all arrays, the caller's. */
+int32_t s3a_queue_events(int32_t groups, int32_t n_lanes, int32_t boundary, int32_t n_utt, const int32_t *n_frames, const int32_t *epoch0,
+                         int32_t *sizes, int32_t *lane, int32_t *f0, int32_t *epoch, int32_t *last_utt, int32_t *epoch_after,
+                         int32_t *nfr_after, int32_t *events, int32_t *lists);
 /* the plan of a call that goes through ku_frames (csrc/s3a_kfplan.h has the terms), host arithmetic on the lengths alone (no device):
  * rule 0 = the plain queue (parts of `budget` rows), 1 = the second-pass queue (longest first, parts of `budget` lanes), 2 = one part,
  * lane z = utterance z; n1 > 0: the first n1 takes scored beside the search, a lead of lead_groups groups up front, rounds of

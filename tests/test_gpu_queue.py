@@ -103,6 +103,27 @@ def test_a_lane_whose_utterance_overflowed_is_scrubbed_on_the_device(gpu_lib, ti
         assert bytes(a[0]) == bytes(b[0]) and np.array_equal(a[1], b[1])
 
 
+@pytest.mark.parametrize("env", [{"S3A_UTT_WIN": "8"}, {"S3A_UTT_WIN": "0"}, {"S3A_UTT_GRAPH": "1"}], ids=["window8", "per_frame", "graph"])
+def test_ends_and_begins_that_share_a_boundary(gpu_lib, tidigits_bundle, monkeypatch, env):
+    """The smallest queue at which the refill schedule (csrc/s3a_qsched.h) can go wrong: lengths on and one past the 8-frame boundary over 2
+    lanes, so that at the same event one lane ends an utterance and begins the next while the other ends, begins or runs on (test_queue_events.py
+    case f has the events).  Through window scoring, scoring per frame and graph blocks, each utterance's header and words are those of a
+    lock-step decode of the same utterances on a second engine."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    _, feats = tidigits_feats(gpu_lib)
+    short = [feats[k][:n].copy() for k, n in enumerate([16, 17, 8, 9, 24, 1])]
+    dec, lock = bundle.Decoder(tidigits_bundle, 2), bundle.Decoder(tidigits_bundle, 2)
+    dec.decode_queue(short)
+    assert dec.ud.last_parts()["n_frames"] == 0               # (the frame as launches: the routes that follow the schedule)
+    for i in range(0, 6, 2):
+        lock.decode(short[i:i + 2])
+        for u in (i, i + 1):
+            a, b = dec.queue_hyp(u, f"s{u}", u), lock.hyp_var(u - i, f"s{u}", u)
+            print(f"utterance {u}: {len(short[u])} frames, status {a[0].status}, {a[0].n_words} words, score {a[0].score}")
+            assert bytes(a[0]) == bytes(b[0]) and np.array_equal(a[1], b[1]), u
+
+
 def test_second_pass_inside_the_queue_through_the_c_abi(gpu_lib, tidigits_bundle):
     """s3a_uttdec_enable_bestpath + s3a_uttdec_decode_queue: the second pass of a lane runs at its refill event; per utterance
     the record of a lock-step decode's s3a_uttdec_bestpath_hyp, words, scores and frame normalisers"""
